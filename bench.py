@@ -19,6 +19,11 @@ MI355X, so replicas scale weakly with N):
      bracketed by barrier + device synchronize; value = generated tokens over
      all ranks / max rank time.
 
+A plain run does only that (CR->ready is then the in-process deploy time).  ``--full`` adds the
+measurements that take runs of their own: CR->ready over fresh predictor processes, the same
+load served over HTTP, and on N > 1 ranks the TP = N and EP = N phases.  ``--dump-outputs DIR``
+writes the last timed step's outputs as ``.npy`` files (seeded inputs: comparable across builds).
+
 Synthetic data, random-init weights (no checkpoints / datasets offline).
 """
 from __future__ import annotations
@@ -43,6 +48,18 @@ def parse(argv=None):
                          "before it makes any HIP call")
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=40)
+    ap.add_argument("--full", action="store_true",
+                    help="also take every measurement beside the headline value, each in runs of its own: "
+                         "CR -> ready over fresh predictor processes (--cr-ready-samples 3), the HTTP-served "
+                         "rate of the same config (--http-check), and with more than one rank the TP and EP "
+                         "phases (--tp-phase / --ep-phase).  Without it a run deploys, warms up, times "
+                         "--steps engine steps and prints the line; each of those options still forces its "
+                         "own measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed engine step returned to its "
+                         "caller (the StepBatch arrays: seq_ids, tokens, finished) as DIR/<name>.npy in "
+                         "float64; ranks past 0 write DIR/<name>.rank<r>.npy.  Prompts and weights are "
+                         "seeded, so two builds can be compared array for array")
     ap.add_argument("--model", default="llama3-8b")
     ap.add_argument("--batch", type=int, default=2048,
                     help="concurrent requests per GPU: 288 GB of HBM holds their ~100 GB of KV pages, and "
@@ -96,8 +113,8 @@ def parse(argv=None):
                     help="also measure the served rate over HTTP at this config (a fresh predictor process "
                          "through operator + ProcessLauncher + V2 clients, runtime/http_bench.py) BEFORE the "
                          "engine-direct run, and report it as served_tokens_per_sec_http; its window is "
-                         "max(--steps, 40) engine steps.  -1 (default): on for the 1-GPU operator bench, "
-                         "off otherwise; 0 / 1 force it")
+                         "max(--steps, 40) engine steps.  -1 (default): on for the 1-GPU operator bench "
+                         "under --full, off otherwise; 0 / 1 force it")
     ap.add_argument("--ab-ops", default="",
                     help="A/B runs: comma list of op=value set through torch.ops.mlop before the engine "
                          "is built, e.g. gemm_half_tile=0 (in-process switches, scripts/ab.sh)")
@@ -105,7 +122,7 @@ def parse(argv=None):
                     help="after the DP replicas (the line's value), run a short TP = world phase of the same "
                          "model on the same ranks: RCCL process group + the K15 IPC all-reduce across the "
                          "devices (xGMI), with K15's start-up self-check and a greedy-token check against a "
-                         "dense TP = 1 recompute, reported as the 'tp' block.  auto: on when world > 1")
+                         "dense TP = 1 recompute, reported as the 'tp' block.  auto: on under --full when world > 1")
     ap.add_argument("--tp-batch", type=int, default=256, help="concurrent requests of the TP phase")
     ap.add_argument("--tp-steps", type=int, default=10, help="timed engine steps of the TP phase")
     ap.add_argument("--tp-warmup", type=int, default=3)
@@ -119,16 +136,22 @@ def parse(argv=None):
     ap.add_argument("--ep-phase", choices=("auto", "on", "off"), default="auto",
                     help="after the TP phase, a short EP = world phase of --ep-model (config 5: DP attention, every "
                          "MoE layer an expert exchange over IPC peer memory across the devices), with a greedy-token "
-                         "check against the dense fp32 EP = 1 model, reported as the 'ep' block.  auto: on when "
-                         "world > 1")
+                         "check against the dense fp32 EP = 1 model, reported as the 'ep' block.  auto: on under "
+                         "--full when world > 1")
     ap.add_argument("--ep-model", default="mixtral-8x7b")
     ap.add_argument("--ep-batch", type=int, default=256, help="concurrent requests PER RANK in the EP phase")
     ap.add_argument("--phase-child", choices=("tp", "ep"), default=None, help=argparse.SUPPRESS)
-    ap.add_argument("--cr-ready-samples", type=int, default=3,
+    ap.add_argument("--cr-ready-samples", type=int, default=None,
                     help="CR -> ready measurements with the predictor as a FRESH OS process (operator -> "
                          "ProcessLauncher -> /v2/health/ready), taken before the serving run on rank 0's GPU; "
-                         "their median is p50_cr_ready_s.  0: report the in-process deploy time instead")
-    return ap.parse_args(argv)
+                         "their median is p50_cr_ready_s.  0: report the in-process deploy time instead.  "
+                         "Default: 3 under --full (or with --http-check 1, which rides on the probe), else 0")
+    a = ap.parse_args(argv)
+    if a.cr_ready_samples is None:
+        a.cr_ready_samples = 3 if a.full or a.http_check == 1 else 0
+    if a.dump_outputs and a.http:
+        ap.error("--dump-outputs: the engine-direct run's outputs; --http serves from another process")
+    return a
 
 
 def _gpu_count() -> int:
@@ -143,7 +166,7 @@ def _gpu_count() -> int:
 def _http_check_on(a, world: int) -> bool:
     if a.http_check >= 0:
         return bool(a.http_check)
-    return world == 1 and not a.no_operator and a.tp == 1 and a.ep == 1
+    return a.full and world == 1 and not a.no_operator and a.tp == 1 and a.ep == 1
 
 
 def _process_ready(a, device_index: int | None, http: bool = False) -> dict:
@@ -328,10 +351,13 @@ def main(argv=None):
     # the first chunk is backed).  A partly backed pool admits fewer prompts, which turns
     # mixed steps into decode-only ones (29.9k vs 32.1k tok/s right after the GPU test suite)
     deploy_info.update(engine.kv.wait_ready())
+    last_out = []
     gen, elapsed, stats, ramp = serve_closed_loop(
         engine, a, a.batch, a.steps, a.warmup, rank,
-        ep_group=engine.model.ps.ep_cpu if a.ep > 1 else None)
+        ep_group=engine.model.ps.ep_cpu if a.ep > 1 else None, last_out=last_out)
     deploy_info["ramp_steps"] = ramp
+    if a.dump_outputs:
+        _dump_outputs(a.dump_outputs, rank, last_out[-1] if last_out else [])
     if a.tp > 1:
         engine.shutdown()  # release the TP workers before the result gather
     res = _report(a, rank, world, dev, float(gen), elapsed, ready_s, stats, deploy_info, engine, proc_ready)
@@ -484,13 +510,13 @@ def _phase_child_main(a) -> None:
 def _ep_phase_on(a, world: int) -> bool:
     if a.ep_phase == "off" or a.tp > 1 or a.ep > 1:
         return False
-    return world > 1 or a.ep_phase == "on"
+    return (a.full and world > 1) or a.ep_phase == "on"
 
 
 def _tp_phase_on(a, world: int) -> bool:
     if a.tp_phase == "off" or a.tp > 1 or a.ep > 1:
         return False
-    return world > 1 or a.tp_phase == "on"
+    return (a.full and world > 1) or a.tp_phase == "on"
 
 
 _EMITTED = []
@@ -505,14 +531,15 @@ def _emit(res) -> None:
     print(json.dumps(res), flush=True)
 
 
-def serve_closed_loop(engine, a, batch, steps, warmup, rank, ep_group=None):
+def serve_closed_loop(engine, a, batch, steps, warmup, rank, ep_group=None, last_out=None):
     """Closed-loop load: ``batch`` concurrent requests of ``--prompt-len`` random tokens and
     ``--output-len`` generated ones, the first cohort at staggered remaining lengths (steady-state
     age mix), each finished request replaced at once.  An untimed ramp admits and prefills the
     first cohort, then ``warmup`` untimed and ``steps`` timed engine steps bracketed by
     ``sync_point`` (device sync + world barrier, TP workers included).  Returns
     (generated tokens, seconds, step-stat deltas, ramp steps).  ``ep_group``: EP ranks step in
-    lock-step, so the ramp continues while ANY rank still ramps."""
+    lock-step, so the ramp continues while ANY rank still ramps.  ``last_out``: a list that
+    receives what the last timed ``engine.step()`` returned (``--dump-outputs``)."""
     from mlopamd.runtime.sampler import SamplingParams
 
     rng = np.random.default_rng(1234 + rank)
@@ -530,13 +557,16 @@ def serve_closed_loop(engine, a, batch, steps, warmup, rank, ep_group=None):
     for i in range(batch):
         new_request(1 + (i * O) // batch)
 
-    def run_steps(n):
+    def run_steps(n, keep=None):
         gen = 0
+        outs = None
         for _ in range(n):
             outs = engine.step()
             gen += len(outs)
             for _ in outs.finished:
                 new_request(O)
+        if keep is not None and outs is not None:
+            keep.append(outs)
         return gen
 
     # ramp (untimed, not counted as warmup): the first cohort's prompts are all
@@ -576,11 +606,25 @@ def serve_closed_loop(engine, a, batch, steps, warmup, rank, ep_group=None):
     engine.sync_point()  # device sync + world barrier (TP workers join it)
     s0 = dict(engine.stats)
     t_start = time.perf_counter()
-    gen = run_steps(steps)
+    gen = run_steps(steps, last_out)
     engine.sync_point()
     elapsed = time.perf_counter() - t_start
     stats = {k: engine.stats[k] - s0.get(k, 0) for k in engine.stats}
     return gen, elapsed, stats, ramp
+
+
+def _dump_outputs(out_dir: str, rank: int, outs) -> None:
+    """``--dump-outputs``: the last timed step's ``StepBatch`` as the caller got it, one float64
+    array per field in the step's own row order (token ids and sequence ids are exact in
+    float64; a few thousand values each, far below any size limit)."""
+    from mlopamd.runtime.engine import StepBatch
+
+    if not isinstance(outs, StepBatch):
+        outs = StepBatch.from_list(list(outs))
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = f".rank{rank}" if rank else ""
+    for name, arr in (("seq_ids", outs.seq_ids), ("tokens", outs.tokens), ("finished", outs.fin)):
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), np.asarray(arr).astype(np.float64))
 
 
 def http_main(a):

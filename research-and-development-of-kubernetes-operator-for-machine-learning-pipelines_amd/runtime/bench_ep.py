@@ -1,7 +1,7 @@
 """The benchmark's expert-parallel phase: Mixtral-8x7B EP = world over the same GPUs (config 5).
 
-After the Llama-3 DP replicas and the TP = N phase (runtime/bench_tp.py), ``bench.py --gpus N``
-serves a short EP = N phase of Mixtral-8x7B in child processes, reported as the JSON line's
+After the Llama-3 DP replicas and the TP = N phase (runtime/bench_tp.py), ``bench.py --gpus N
+--full`` serves a short EP = N phase of Mixtral-8x7B in child processes, reported as the JSON line's
 ``ep`` block, so the one run on an N-GPU node also carries the expert exchange across devices
 (CL4 over IPC peer memory, ops/csrc/ep_exchange.hip; RCCL all-to-all without it):
 

@@ -3,8 +3,8 @@
 ``bench.py --gpus N`` measures N data-parallel Llama-3 replicas (the reference's predictor
 ``replicas``, /root/reference/mlflow_operator.py:204-205,219-220), whose only collective is
 the result gather.  So that the one run on an N-GPU node also says something about configs 4
-and 5 (TP over RCCL + xGMI), the same ranks then free their DP engines and serve a short
-TP = N phase of the same model, reported as the JSON line's ``tp`` block:
+and 5 (TP over RCCL + xGMI), under ``--full`` the same ranks then free their DP engines and
+serve a short TP = N phase of the same model, reported as the JSON line's ``tp`` block:
 
   1. every rank random-initialises the FULL model (same seed: identical weights on every
      device, on-device RNG) and copies its Megatron shard out of it (``load_shard_from``);

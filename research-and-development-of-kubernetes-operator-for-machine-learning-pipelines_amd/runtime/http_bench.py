@@ -95,7 +95,7 @@ async def cr_ready_process(model: str = "llama3-8b", batch: int = 2048, engine_e
                            samples: int = 1, gpus=None, ready_timeout_s: float = 900.0) -> dict:
     """CR -> ready with the predictor as a FRESH OS process (process start, imports, HIP init,
     weights, KV pool, graph capture all inside), ``samples`` times on a fresh stack each; the
-    predictor is torn down again.  The default ``bench.py`` line reports its median as
+    predictor is torn down again.  The ``bench.py --full`` line reports its median as
     ``p50_cr_ready_s``."""
     vals, last = [], {}
     for _ in range(max(1, samples)):

@@ -32,7 +32,7 @@ TP_ARGS = ["--tp-batch", "16", "--tp-steps", "3", "--tp-warmup", "1", "--ep-mode
 
 
 def test_bench_single_process_json():
-    d = _run([sys.executable, os.path.join(ROOT, "bench.py"), *ARGS])
+    d = _run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", *ARGS])
     assert KEYS <= set(d)
     assert d["n_gpus"] == 1 and d["steps"] == 4 and d["warmup"] == 2 and d["value"] > 0
     assert d["config"]["parallelism"] == "dp1" and d["higher_is_better"] is True
@@ -48,6 +48,31 @@ def test_bench_single_process_json():
     assert "served_tokens_per_sec_http" in d  # None on CPU unless forced (below)
 
 
+def test_bench_plain_run_is_lean_and_dumps_reproducible_outputs(tmp_path):
+    """Without ``--full`` the run takes no measurement beside the headline (no fresh predictor
+    processes, no HTTP run); ``--steps`` sets the timed steps, and ``--dump-outputs`` writes the
+    last timed step's StepBatch as float64 arrays that a second run reproduces exactly."""
+    import numpy as np
+
+    dumps = []
+    for name in ("a", "b"):
+        d = _run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--model", "tiny-llama",
+                  "--batch", "8", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / name)])
+        assert KEYS <= set(d) and d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0
+        mix = d["step_mix"]  # the timed window's counters: exactly the 3 steps asked for
+        assert sum(mix.get(k, 0) for k in ("decode_steps", "mixed_steps", "prefill_steps")) == 3, mix
+        assert d["cr_ready_path"] == "in-process" and d["cr_ready_process"] is None
+        assert d["served_tokens_per_sec_http"] is None and "tp" not in d and "ep" not in d
+        files = sorted(os.listdir(tmp_path / name))
+        assert files == ["finished.npy", "seq_ids.npy", "tokens.npy"]
+        dumps.append({f: np.load(tmp_path / name / f) for f in files})
+    a, b = dumps
+    n = len(a["tokens.npy"])
+    assert 0 < n <= 8
+    for f in a:
+        assert a[f].dtype == np.float64 and a[f].shape == (n,) and np.array_equal(a[f], b[f])
+
+
 def test_bench_reports_http_served_rate():
     """``--http-check 1``: the default line also carries the HTTP-served rate of the same config
     (fresh predictor process, operator + Router + V2 clients) measured before the engine run."""
@@ -61,7 +86,7 @@ def test_bench_reports_http_served_rate():
 def test_bench_two_ranks_gloo():
     d = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
               "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-              os.path.join(ROOT, "bench.py"), "--gpus", "2", "--cr-ready-samples", "0", *ARGS, *TP_ARGS])
+              os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--cr-ready-samples", "0", *ARGS, *TP_ARGS])
     assert d["dist"] == {"world_size": 2, "backend": "gloo", "launcher": "torch.distributed.run"}
     assert d["n_gpus"] == 2 and d["config"]["parallelism"] == "dp2"
     assert d["config"]["global_batch"] == 16 and d["value"] > 0
@@ -87,7 +112,7 @@ def test_bench_two_ranks_gloo():
 def test_bench_tp_phase_watchdog_keeps_the_dp_result():
     """A TP phase that overruns --tp-timeout (a first-contact hang on real peers) must not cost
     the DP value: rank 0 prints THE line with tp.error and every rank exits 0."""
-    d = _run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--cr-ready-samples", "0",
+    d = _run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--cr-ready-samples", "0",
               *ARGS, "--tp-batch", "64", "--tp-steps", "200", "--tp-timeout", "3", "--ep-phase", "off"])
     assert d["value"] > 0 and d["n_gpus"] == 2
     assert "tp-timeout" in d["tp"]["error"] and d["tp"]["child_rc"] == 3
@@ -96,7 +121,7 @@ def test_bench_tp_phase_watchdog_keeps_the_dp_result():
 def test_bench_phase_budget_skips_what_does_not_fit():
     """The TP and EP phases share ``--phase-budget``: a hang in the first cannot push the command
     past the driver's limit.  With less than 30 s of budget, both say so and do not start."""
-    d = _run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--cr-ready-samples", "0",
+    d = _run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--cr-ready-samples", "0",
               *ARGS, *TP_ARGS, "--phase-budget", "25"])
     assert d["value"] > 0 and d["n_gpus"] == 2
     assert d["tp"]["error"].startswith("skipped") and d["ep"]["error"].startswith("skipped")
@@ -106,7 +131,7 @@ def test_bench_tp_phase_child_crash_keeps_the_dp_result():
     """A rank of the TP phase that dies outright (abort: what a GPU fault does to a process) ends
     only its child process: the DP ranks still print THE line, with tp.error, and exit 0."""
     env = dict(os.environ, OMP_NUM_THREADS="2", MLOP_INJECT_TP_PHASE_ABORT="0")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--cr-ready-samples", "0",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--cr-ready-samples", "0",
                         *ARGS, *TP_ARGS, "--tp-timeout", "20", "--ep-phase", "off"], cwd="/tmp",
                        capture_output=True, text=True,
                        timeout=600, env=env)
@@ -121,7 +146,7 @@ def test_bench_self_launches_n_ranks():
     """``python bench.py --gpus 2`` with no torchrun around it (the driver's plain command):
     bench.py launches the 2 rank processes itself, both replicas' tokens are counted, and
     the line says which world actually ran."""
-    d = _run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", *ARGS, *TP_ARGS])
+    d = _run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", *ARGS, *TP_ARGS])
     assert d["n_gpus"] == 2 and d["config"]["parallelism"] == "dp2"
     assert d["tp"]["tokens_per_sec"] > 0 and d["tp"]["first_token_match"]
     assert d["dist"] == {"world_size": 2, "backend": "gloo", "launcher": "bench.py"}

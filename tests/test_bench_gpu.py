@@ -16,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_two_ranks_share_gpu_tp_ep_phases():
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu", "--kv-gb", "4",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--share-gpu", "--kv-gb", "4",
            "--model", "tiny-llama", "--batch", "16", "--steps", "4", "--warmup", "2", "--cr-ready-samples", "0",
            "--tp-batch", "16", "--tp-steps", "3", "--tp-warmup", "1", "--ep-model", "tiny-mixtral",
            "--ep-batch", "16", "--phase-budget", "200"]
