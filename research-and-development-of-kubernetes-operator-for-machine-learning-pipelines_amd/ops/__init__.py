@@ -702,7 +702,76 @@ def sample(logits, temps, top_ks, top_ps, uniform, full: bool | None = None) -> 
     return out
 
 
-__all__ = ["argmax", "sample", "load","available", "library_path", "rmsnorm", "add_rmsnorm", "rope_cache",
+PENALTY_PROMPT_BIT = -(2**31)  # int32 bit 31 of a count-table word: the id occurs in the prompt
+
+
+def penalty_table(slots: int, vocab: int, device) -> torch.Tensor:
+    """The penalty count table, int32 [slots, ldt] zeroed; ldt = vocab rounded up to 4 so every
+    row starts on a 16-B boundary.  Bit 31 = in the prompt, bits 0..30 = count in the output."""
+    return torch.zeros(slots, (vocab + 3) // 4 * 4, dtype=torch.int32, device=device)
+
+
+def _ids64(ids, device) -> torch.Tensor:
+    if isinstance(ids, torch.Tensor):
+        return ids.to(device=device, dtype=torch.int64).contiguous().view(-1)
+    return torch.tensor(list(ids), dtype=torch.int64).to(device)
+
+
+def penalty_reset(table: torch.Tensor, slot: int, prompt_ids, output_ids, vocab: int | None = None) -> None:
+    """Row ``slot`` of the table := the state of a request with this prompt and this output so
+    far (prompt ids may repeat; every output id counts once per occurrence)."""
+    vocab = table.shape[1] if vocab is None else vocab
+    p, o = _ids64(prompt_ids, table.device), _ids64(output_ids, table.device)
+    if not table.is_cuda:
+        row = table[slot]
+        row.zero_()
+        p, o = p[(p >= 0) & (p < vocab)], o[(o >= 0) & (o < vocab)]
+        row[p] = PENALTY_PROMPT_BIT
+        row += torch.bincount(o, minlength=row.numel()).to(torch.int32)
+        return
+    _need_gpu()
+    torch.ops.mlop.penalty_reset(table, int(slot), int(vocab), p, o)
+
+
+def penalty_update(table: torch.Tensor, slots: torch.Tensor, tokens: torch.Tensor, vocab: int | None = None) -> None:
+    """table[slots[i], tokens[i]] += 1 for every i with slots[i] >= 0 (after the draw)."""
+    vocab = table.shape[1] if vocab is None else vocab
+    if not table.is_cuda:
+        for s, t in zip(slots.tolist(), tokens.tolist()):
+            if 0 <= s < table.shape[0] and 0 <= t < vocab:
+                table[s, t] += 1
+        return
+    _need_gpu()
+    torch.ops.mlop.penalty_update(table, int(vocab), slots, tokens.contiguous())
+
+
+def apply_penalties(logits: torch.Tensor, table: torch.Tensor, slots, rep, freq, pres) -> torch.Tensor:
+    """Repetition / frequency / presence penalties, in place on fp32 ``logits`` [n, V]; rows with
+    ``slots[i] < 0`` are not touched."""
+    if not logits.is_cuda:
+        from ..runtime.sampler import penalties_reference
+
+        return penalties_reference(logits, table, slots, rep, freq, pres)
+    _need_gpu()
+    torch.ops.mlop.apply_penalties(logits, table, slots, rep, freq, pres)
+    return logits
+
+
+def token_logprobs(out_lp: torch.Tensor, out_id: torch.Tensor, logits: torch.Tensor, chosen: torch.Tensor,
+                   want: torch.Tensor) -> None:
+    """Row i with want[i] = N >= 0: out[i, 0] = (chosen[i], its log-softmax over the whole row),
+    out[i, 1..N] = the N largest logits' (id, log-softmax), value descending, ties by lower id.
+    Rows with want[i] < 0 and columns past N keep what they held.  ``logits``: bf16 or fp32."""
+    if not logits.is_cuda:
+        from ..runtime.sampler import logprobs_reference
+
+        return logprobs_reference(out_lp, out_id, logits, chosen, want)
+    _need_gpu()
+    torch.ops.mlop.token_logprobs(out_lp, out_id, logits, chosen.contiguous(), want)
+
+
+__all__ = ["argmax", "sample", "penalty_table", "penalty_reset", "penalty_update", "apply_penalties",
+           "token_logprobs", "load","available", "library_path", "rmsnorm", "add_rmsnorm", "rope_cache",
            "silu_mul", "embedding", "paged_attention", "ref"]
 
 

@@ -714,6 +714,91 @@ void sample(Tensor out, Tensor logits, Tensor temps, Tensor top_ks, Tensor top_p
 }
 
 
+// ---- sampler extensions: penalty count table, penalties, token log-probabilities ----
+void check_table(const Tensor& table) {
+  check_i32(table, "penalty table");
+  TORCH_CHECK(table.dim() == 2 && table.size(1) % 4 == 0 &&
+                  reinterpret_cast<uintptr_t>(table.data_ptr()) % 16 == 0,
+              "penalty table must be int32 [slots, ldt] with ldt % 4 == 0 and 16-B aligned");
+}
+void check_ids(const Tensor& t, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kLong && t.is_contiguous() && t.dim() == 1, name,
+              " must be a contiguous int64 [n] GPU tensor");
+}
+void check_f32n(const Tensor& t, int64_t n, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat && t.is_contiguous() && t.numel() == n, name,
+              " must be a contiguous f32 [n] GPU tensor");
+}
+
+void penalty_reset(Tensor table, int64_t slot, int64_t vocab, Tensor prompt_ids, Tensor output_ids) {
+  check_table(table);
+  check_ids(prompt_ids, "prompt_ids");
+  check_ids(output_ids, "output_ids");
+  TORCH_CHECK(slot >= 0 && slot < table.size(0), "penalty slot out of range");
+  TORCH_CHECK(vocab > 0 && vocab <= table.size(1), "vocab must be in (0, ldt]");
+  c10::DeviceGuard g(table.device());
+  mlop::launch_penalty_reset(table.data_ptr<int>() + slot * table.size(1), (int)vocab, (int)table.size(1),
+                             (const long*)prompt_ids.data_ptr<int64_t>(), (int)prompt_ids.numel(),
+                             (const long*)output_ids.data_ptr<int64_t>(), (int)output_ids.numel(), cur_stream());
+}
+
+void penalty_update(Tensor table, int64_t vocab, Tensor slots, Tensor tokens) {
+  check_table(table);
+  check_i32(slots, "slots");
+  check_ids(tokens, "tokens");
+  TORCH_CHECK(slots.numel() == tokens.numel(), "slots / tokens length");
+  TORCH_CHECK(vocab > 0 && vocab <= table.size(1), "vocab must be in (0, ldt]");
+  c10::DeviceGuard g(table.device());
+  mlop::launch_penalty_update(table.data_ptr<int>(), table.size(1), (int)vocab, (int)table.size(0),
+                              slots.data_ptr<int>(), (const long*)tokens.data_ptr<int64_t>(), (int)tokens.numel(),
+                              cur_stream());
+}
+
+void apply_penalties(Tensor logits, Tensor table, Tensor slots, Tensor rep, Tensor freq, Tensor pres) {
+  check_logits(logits);
+  check_table(table);
+  const int64_t n = logits.size(0);
+  check_i32(slots, "slots");
+  TORCH_CHECK(slots.numel() == n, "slots");
+  check_f32n(rep, n, "rep");
+  check_f32n(freq, n, "freq");
+  check_f32n(pres, n, "pres");
+  TORCH_CHECK(logits.size(1) <= table.size(1), "the table's rows are shorter than the vocabulary");
+  c10::DeviceGuard g(logits.device());
+  mlop::launch_apply_penalties(logits.data_ptr<float>(), (int)n, (int)logits.size(1), logits.stride(0),
+                               table.data_ptr<int>(), table.size(1), (int)table.size(0), slots.data_ptr<int>(),
+                               rep.data_ptr<float>(), freq.data_ptr<float>(), pres.data_ptr<float>(), cur_stream());
+}
+
+void token_logprobs(Tensor out_lp, Tensor out_id, Tensor logits, Tensor chosen, Tensor want) {
+  const bool bf = logits.scalar_type() == at::kBFloat16;
+  if (bf) {
+    TORCH_CHECK(logits.is_cuda() && logits.dim() == 2 && logits.stride(1) == 1 && logits.stride(0) % 8 == 0 &&
+                    reinterpret_cast<uintptr_t>(logits.data_ptr()) % 16 == 0,
+                "bf16 logits must be [n, V] with unit inner stride and 16-B aligned rows");
+  } else {
+    check_logits(logits);
+  }
+  const int64_t n = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(out_lp.is_cuda() && out_lp.scalar_type() == at::kFloat && out_lp.is_contiguous() &&
+                  out_lp.dim() == 2 && out_lp.size(0) == n && out_lp.size(1) >= 1,
+              "out_lp must be a contiguous f32 [n, 1 + N]");
+  check_i32(out_id, "out_id");
+  TORCH_CHECK(out_id.sizes() == out_lp.sizes(), "out_id must have out_lp's shape");
+  check_ids(chosen, "chosen");
+  check_i32(want, "want");
+  TORCH_CHECK(chosen.numel() == n && want.numel() == n, "chosen / want length");
+  TORCH_CHECK(mlop::logprob_splits((int)n, (int)V) > 0, "vocabulary too large for token_logprobs");
+  c10::DeviceGuard g(logits.device());
+  if (n == 0) return;
+  at::Tensor ws = at::empty({mlop::logprob_workspace_bytes((int)n, (int)V)}, logits.options().dtype(at::kByte));
+  mlop::launch_token_logprobs(out_lp.data_ptr<float>(), out_id.data_ptr<int>(), (int)out_lp.size(1),
+                              logits.data_ptr(), bf, (int)n, (int)V, logits.stride(0),
+                              (const long*)chosen.data_ptr<int64_t>(), want.data_ptr<int>(), ws.data_ptr(),
+                              cur_stream());
+}
+
+
 // ---- K15 custom all-reduce: host-side state, int handles -------------------
 int64_t car_create(int64_t rank, int64_t world, int64_t max_bytes, int64_t device, bool split) {
   return mlop::car_create((int)rank, (int)world, (long)max_bytes, (int)device, split ? 1 : 0);
@@ -946,6 +1031,11 @@ TORCH_LIBRARY(mlop, m) {
   m.def("argmax(Tensor(a!) out, Tensor logits) -> ()");
   m.def("sample(Tensor(a!) out, Tensor logits, Tensor temps, Tensor top_ks, Tensor top_ps, "
         "Tensor uniform, bool full) -> ()");
+  m.def("penalty_reset(Tensor(a!) table, int slot, int vocab, Tensor prompt_ids, Tensor output_ids) -> ()");
+  m.def("penalty_update(Tensor(a!) table, int vocab, Tensor slots, Tensor tokens) -> ()");
+  m.def("apply_penalties(Tensor(a!) logits, Tensor table, Tensor slots, Tensor rep, Tensor freq, "
+        "Tensor pres) -> ()");
+  m.def("token_logprobs(Tensor(a!) out_lp, Tensor(b!) out_id, Tensor logits, Tensor chosen, Tensor want) -> ()");
   m.def("rmsnorm(Tensor(a!) out, Tensor x, Tensor w, float eps) -> ()");
   m.def("add_rmsnorm(Tensor(a!) out, Tensor(b!) residual, Tensor x, Tensor w, float eps) -> ()");
   m.def("rope_cache(Tensor(a!) q_out, Tensor(b!) k_cache, Tensor(c!) v_cache, Tensor qkv, "
@@ -986,6 +1076,10 @@ TORCH_LIBRARY_IMPL(mlop, CUDA, m) {
   m.impl("moe_combine", &moe_combine);
   m.impl("argmax", &argmax);
   m.impl("sample", &sample);
+  m.impl("penalty_reset", &penalty_reset);
+  m.impl("penalty_update", &penalty_update);
+  m.impl("apply_penalties", &apply_penalties);
+  m.impl("token_logprobs", &token_logprobs);
   m.impl("car_all_reduce", &car_all_reduce);
   m.impl("car_all_reduce_add", &car_all_reduce_add);
   m.impl("car_broadcast", &car_broadcast);

@@ -206,6 +206,21 @@ long sample_workspace_bytes(int n, int V);
 void launch_sample(long* out, const float* logits, int n, int V, long ld, const float* temps,
                    const int* top_ks, const float* top_ps, const float* uniform, void* ws, bool full,
                    hipStream_t st);
+// sampler extensions (sampling_ext.hip).  Count table int32 [nslots, ldt >= V] (ldt % 4 == 0): bit 31 =
+// in the prompt, bits 0..30 = occurrences in the output
+void launch_penalty_reset(int* row, int V, int ldt, const long* prompt, int np, const long* output, int no,
+                          hipStream_t st);
+void launch_penalty_update(int* table, long ldt, int V, int nslots, const int* slots, const long* tokens, int n,
+                           hipStream_t st);
+void launch_apply_penalties(float* logits, int n, int V, long ld, const int* table, long ldt, int nslots,
+                            const int* slots, const float* rep, const float* freq, const float* pres,
+                            hipStream_t st);
+// log-softmax at `chosen` (column 0) and of the top want[i] <= 20 logits (columns 1..) of bf16 / fp32 rows;
+// logprob_splits = 0: the vocabulary is too large; ws: logprob_workspace_bytes(n, V) bytes
+int logprob_splits(int n, int V);
+long logprob_workspace_bytes(int n, int V);
+void launch_token_logprobs(float* out_lp, int* out_id, int ldo, const void* logits, bool bf16, int n, int V,
+                           long ld, const long* chosen, const int* want, void* ws, hipStream_t st);
 
 // lazily backed KV arenas (vmm.hip): reserve VA, back chunks synchronously or on a native
 // worker thread; the returned owner must outlive every use of the range

@@ -12,21 +12,11 @@
 
 #include "common.h"
 #include "launch.h"
+#include "sampling_common.h"
 
 namespace mlop {
 
-constexpr int kSampleThreads = 256;
 constexpr int kMaxCand = 1024;
-
-__device__ __forceinline__ uint32_t fkey(float f) {
-  uint32_t b = __float_as_uint(f);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-
-// (value, index) argmax with ties to the smallest index; NaN never wins
-__device__ __forceinline__ void amax_merge(float& v, int& i, float ov, int oi) {
-  if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
-}
 
 __device__ void block_argmax(const float* __restrict__ row, int V, float* sv, int* si,
                              float& best_v, int& best_i) {

@@ -61,13 +61,14 @@ def load_tokenizer(checkpoint_dir):
 
 
 class _Req:
-    __slots__ = ("prompt", "params", "loop", "future", "queue", "tokens", "t0", "t_first", "seq")
+    __slots__ = ("prompt", "params", "loop", "future", "queue", "tokens", "t0", "t_first", "seq", "logprobs")
 
     def __init__(self, prompt, params, loop, stream):
         self.prompt, self.params, self.loop = prompt, params, loop
         self.future = loop.create_future()
         self.queue = asyncio.Queue() if stream else None
         self.tokens, self.t0, self.t_first, self.seq = [], time.perf_counter(), None, None
+        self.logprobs = [] if params.logprobs is not None else None  # one entry per completion token
 
 
 class LLMBackend:
@@ -134,13 +135,20 @@ class LLMBackend:
                         self.metrics.ttft.labels(**self.metrics.labels).observe(now - r.t0)
                         self.metrics.tokens_in.labels(**self.metrics.labels).inc(len(r.prompt))
                 r.tokens.append(o.token)
+                item = o.token
+                if r.logprobs is not None:
+                    top = [[int(i), float(v)] for i, v in (o.top_logprobs or ())]
+                    r.logprobs.append({"token_id": o.token, "logprob": o.logprob, "top": top})
+                    item = (o.token, o.logprob, top)
                 if r.queue is not None:
-                    r.loop.call_soon_threadsafe(r.queue.put_nowait, o.token)
+                    r.loop.call_soon_threadsafe(r.queue.put_nowait, item)
                 if o.finished:
                     self._active.pop(o.seq_id, None)
                     res = {"output_ids": list(r.tokens), "finish_reason": o.finish_reason,
                            "ttft": r.t_first - r.t0, "latency": now - r.t0,
                            "prompt_tokens": len(r.prompt)}
+                    if r.logprobs is not None:
+                        res["logprobs"] = r.logprobs
                     if self.metrics:
                         m = self.metrics
                         m.tokens_out.labels(**m.labels).inc(len(r.tokens))

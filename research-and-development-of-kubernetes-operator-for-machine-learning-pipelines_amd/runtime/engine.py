@@ -38,7 +38,7 @@ import torch
 from .. import ops
 from .attn_meta import MetaBuffers, plan_partitions
 from .kv_cache import BLOCK_SIZE, BlockAllocator, KVCache, blocks_for_budget, blocks_needed, prefix_hashes
-from .sampler import Sampler, SamplingParams
+from .sampler import MAX_LOGPROBS, Sampler, SamplerExt, SamplingParams
 from .tracing import StepTracer, TorchProfileWindow
 
 
@@ -178,6 +178,8 @@ class Sequence:
     finish_reason: str | None = None
     hashes: list = field(default_factory=list)  # prefix hashes of this sequence's full pages
     n_reg: int = 0                              # leading pages matched in / registered to the prefix cache
+    pen_slot: int = -1                          # row of the penalty count table held while admitted
+    logprobs: list = field(default_factory=list)  # per output token (logprob, [(id, logprob), ...]) when asked for
 
     @property
     def length(self) -> int:
@@ -217,6 +219,9 @@ class EngineConfig:
     # one-step-ahead scheduling (TP = EP = 1, mixed prefill): step t+1 is built and launched
     # while step t still runs on the device; step t's tokens are read back afterwards
     async_scheduling: bool = True
+    # rows of the penalty count table (int32 [penalty_slots, vocab], allocated on the first
+    # penalised request): penalised requests admitted at once; further ones wait for a slot
+    penalty_slots: int = 64
 
 
 @dataclass
@@ -225,6 +230,8 @@ class StepOutput:
     token: int
     finished: bool
     finish_reason: str | None = None
+    logprob: float | None = None        # SamplingParams.logprobs: the token's log-probability
+    top_logprobs: list | None = None    # ... and the top-N [(id, logprob), ...]
 
 
 class _ParamsList(list):
@@ -247,29 +254,47 @@ class StepBatch:
     """One step's outputs as arrays (no per-token Python objects on the hot path);
     iterating yields ``StepOutput`` lazily."""
 
-    __slots__ = ("seq_ids", "tokens", "fin", "reasons")
+    __slots__ = ("seq_ids", "tokens", "fin", "reasons", "lps")
 
-    def __init__(self, seq_ids, tokens, fin, reasons: dict):
+    def __init__(self, seq_ids, tokens, fin, reasons: dict, lps: dict | None = None):
         self.seq_ids, self.tokens, self.fin, self.reasons = seq_ids, tokens, fin, reasons
+        # seq_id -> (logprob, [(id, logprob), ...]) of the rows that asked for log-probabilities
+        # (a sequence has at most one token per step); None when no row did
+        self.lps = lps or None
 
     @classmethod
     def from_list(cls, outs: list):
         return cls(np.array([o.seq_id for o in outs], dtype=np.int64),
                    np.array([o.token for o in outs], dtype=np.int64),
                    np.array([o.finished for o in outs], dtype=bool),
-                   {o.seq_id: o.finish_reason for o in outs if o.finished})
+                   {o.seq_id: o.finish_reason for o in outs if o.finished},
+                   {o.seq_id: (o.logprob, o.top_logprobs) for o in outs if o.logprob is not None})
+
+    @classmethod
+    def concat(cls, a: "StepBatch", b: "StepBatch"):
+        reasons = dict(a.reasons)
+        reasons.update(b.reasons)
+        lps = None
+        if a.lps or b.lps:
+            lps = dict(a.lps or {})
+            lps.update(b.lps or {})
+        return cls(np.concatenate([a.seq_ids, b.seq_ids]), np.concatenate([a.tokens, b.tokens]),
+                   np.concatenate([a.fin, b.fin]), reasons, lps)
 
     def __len__(self):
         return len(self.seq_ids)
 
+    def _out(self, sid, tok, f):
+        lp = self.lps.get(sid) if self.lps else None
+        return StepOutput(sid, tok, f, self.reasons.get(sid) if f else None, *(lp or ()))
+
     def __iter__(self):
         for sid, tok, f in zip(self.seq_ids.tolist(), self.tokens.tolist(), self.fin.tolist()):
-            yield StepOutput(sid, tok, f, self.reasons.get(sid) if f else None)
+            yield self._out(sid, tok, f)
 
     @property
     def finished(self) -> list:
-        return [StepOutput(int(self.seq_ids[i]), int(self.tokens[i]), True, self.reasons.get(int(self.seq_ids[i])))
-                for i in np.nonzero(self.fin)[0]]
+        return [self._out(int(self.seq_ids[i]), int(self.tokens[i]), True) for i in np.nonzero(self.fin)[0]]
 
 
 class Engine:
@@ -320,6 +345,19 @@ class Engine:
         self.r_nblk = np.zeros(R, np.int64)     # KV pages held
         self.r_sid = np.zeros(R, np.int64)
         self.r_random = np.zeros(R, bool)       # non-greedy sampling
+        # sampler extensions, set when a request takes its row (_admit_ext): the row's slot of the
+        # penalty count table (-1: none), its penalties, the top log-probabilities it wants (-1:
+        # none), and "this row needs the sampler" (non-greedy, penalised or log-probabilities)
+        self.r_pen_slot = np.full(R, -1, np.int32)
+        self.r_rep = np.ones(R, np.float32)
+        self.r_freq = np.zeros(R, np.float32)
+        self.r_pres = np.zeros(R, np.float32)
+        self.r_want = np.full(R, -1, np.int32)
+        self.r_sampler = np.zeros(R, bool)
+        self.pen_table = None  # int32 [penalty_slots, vocab]: allocated by the first request that needs it
+        self.free_pen_slots = list(range(max(0, cfg.penalty_slots) - 1, -1, -1))
+        self._last_lp = None   # the last _sample's (logprobs, ids) device tensors, or None
+        self._lp_h = None      # async: pinned double buffers of the log-probability read-back
         self.r_epoch = np.zeros(R, np.int64)    # bumped when a row is released (async: stale results)
         self.r_tokidx = np.zeros(R, np.int64)   # async: the row's pending token in the in-flight step
         # rows of ``self.running`` in order, and their output lists (kept in step with the
@@ -428,7 +466,9 @@ class Engine:
         V = self.model.cfg.vocab_size
         if min(prompt) < 0 or max(prompt) >= V:
             raise ValueError(f"prompt token ids must be in [0, {V})")
-        (params or SamplingParams()).validate()
+        params = (params or SamplingParams()).validate()
+        if params.penalised and self.cfg.penalty_slots <= 0:
+            raise ValueError("this engine serves no penalised requests (penalty_slots = 0)")
 
     def add_request(self, prompt, params: SamplingParams | None = None, seq_id: int | None = None) -> Sequence:
         params = params or SamplingParams()
@@ -481,7 +521,13 @@ class Engine:
             self.alloc.free(seq.blocks)
             seq.blocks = []
         seq.n_reg = 0
+        if seq.pen_slot >= 0:
+            # the slot's pending penalty_update launches (a speculatively decoded row) are already
+            # on the stream: the next owner's penalty_reset is enqueued behind them
+            self.free_pen_slots.append(seq.pen_slot)
+            seq.pen_slot = -1
         if seq.row >= 0:
+            self.r_pen_slot[seq.row], self.r_want[seq.row] = -1, -1
             self.r_nblk[seq.row] = 0
             self.r_epoch[seq.row] += 1  # an in-flight step's result for this row is stale
             self.free_rows.append(seq.row)
@@ -491,8 +537,39 @@ class Engine:
     def _params_of_running(self):
         """Sampling params of the decode batch; a falsy ``any_random`` lets the sampler
         take the all-greedy fast path without a per-sequence Python scan."""
-        lst = _ParamsList(s.params for s in self.running) if self.r_random[self._sync_rows()].any() else _ALL_GREEDY
+        lst = _ParamsList(s.params for s in self.running) if self.r_sampler[self._sync_rows()].any() else _ALL_GREEDY
         return lst
+
+    def _admit_ext(self, seq: Sequence) -> bool:
+        """A request takes its row: its sampler-extension state.  A penalised request also takes a
+        slot of the count table (False: none free, it waits) and the slot is rebuilt from the
+        prompt (mask) and the output so far (counts: re-admission after preemption), on the
+        engine's stream, so ahead of the first step that draws for it."""
+        r, p = seq.row, seq.params
+        self.r_sampler[r] = (not p.greedy) or p.extended
+        self.r_want[r] = -1 if p.logprobs is None else p.logprobs
+        self.r_pen_slot[r] = -1
+        if not p.penalised:
+            return True
+        if not self.free_pen_slots:
+            return False
+        if self.pen_table is None:
+            self.pen_table = ops.penalty_table(self.cfg.penalty_slots, self.model.cfg.vocab_size, self.device)
+            self.stats["penalty_table_bytes"] = self.pen_table.numel() * 4
+        seq.pen_slot = self.free_pen_slots.pop()
+        ops.penalty_reset(self.pen_table, seq.pen_slot, seq.prompt, seq.output, self.model.cfg.vocab_size)
+        self.r_pen_slot[r] = seq.pen_slot
+        self.r_rep[r], self.r_freq[r], self.r_pres[r] = p.repetition_penalty, p.frequency_penalty, p.presence_penalty
+        return True
+
+    def _ext_of(self, rows):
+        """The sampler-extension arrays of a step's logits rows (None: no row uses them)."""
+        slots, want = self.r_pen_slot[rows], self.r_want[rows]
+        if not ((slots >= 0).any() or (want >= 0).any()):
+            return None
+        self.stats["sampler_ext_rows"] += int(((slots >= 0) | (want >= 0)).sum())
+        return SamplerExt(self.pen_table, slots, self.r_rep[rows], self.r_freq[rows], self.r_pres[rows], want,
+                          self.model.cfg.vocab_size)
 
     def _register_running(self, s: Sequence):
         r, p = s.row, s.params
@@ -622,6 +699,9 @@ class Engine:
             seq = self.waiting[0]
             seq.row = self.free_rows.pop()
             self.rows_hi = max(self.rows_hi, seq.row + 1)
+            if not self._admit_ext(seq):
+                self._release(seq)  # no free slot of the penalty table: it waits, like for a row
+                break
             if self.cfg.enable_prefix_caching:
                 self._match_prefix(seq)
             n = min(seq.length - seq.num_cached, budget)
@@ -675,7 +755,16 @@ class Engine:
             self.alloc.register(seq.blocks[i], seq.hashes[i])
         seq.n_reg = full
 
-    def _prefill_finish(self, batch, ctx, done, tokens) -> list:
+    def _lp_entry(self, lp_h, id_h, i: int, n: int):
+        """Row i of a step's log-probability read-back -> (logprob, [(id, logprob)] * n)."""
+        return float(lp_h[i, 0]), list(zip(id_h[i, 1:1 + n].tolist(), lp_h[i, 1:1 + n].tolist()))
+
+    def _take_lp(self):
+        """The last draw's log-probabilities on the host (numpy pair), or None."""
+        lp, self._last_lp = self._last_lp, None
+        return None if lp is None else (lp[0].cpu().numpy(), lp[1].cpu().numpy())
+
+    def _prefill_finish(self, batch, ctx, done, tokens, lp=None, lp_off: int = 0) -> list:
         outs = []
         ti = 0
         for s, c, d in zip(batch, ctx, done):
@@ -686,7 +775,12 @@ class Engine:
                 self.prefilling.remove(s)
                 s.status = Status.RUNNING
                 self.running.append(s)
+                if lp is not None and s.params.logprobs is not None:
+                    entry = self._lp_entry(lp[0], lp[1], lp_off + ti, s.params.logprobs)
+                    s.logprobs.append(entry)
                 o = self._append(s, tokens[ti])
+                if lp is not None and s.params.logprobs is not None:
+                    o.logprob, o.top_logprobs = entry
                 if not o.finished:
                     self._register_running(s)
                 outs.append(o)
@@ -705,16 +799,18 @@ class Engine:
         part, nparts = plan_partitions(nt, self.model.n_kv, max(ctx))
         done_params = [s.params for s, d in zip(batch, done) if d]
         logits = self._launch(KIND_EAGER, T, nt, nl, part, nparts, 0,
-                              greedy=all(p.greedy for p in done_params))
-        tokens = None
+                              greedy=all(p.greedy and not p.extended for p in done_params))
+        tokens = lp = None
         if nl:
             tokens = self._sample(logits, done_params,
-                                  lambda: [len(s.output) for s, d in zip(batch, done) if d]).tolist()
+                                  lambda: [len(s.output) for s, d in zip(batch, done) if d],
+                                  [s.row for s, d in zip(batch, done) if d]).tolist()
+            lp = self._take_lp()
         else:
             torch.cuda.synchronize() if self.device.type == "cuda" else None
         self.stats["prefill_steps"] += 1
         self.stats["prefill_tokens"] += T
-        return StepBatch.from_list(self._prefill_finish(batch, ctx, done, tokens))
+        return StepBatch.from_list(self._prefill_finish(batch, ctx, done, tokens, lp))
 
     # ------------------------------------------------------------ mixed --
     def _mixed_step(self):
@@ -742,28 +838,26 @@ class Engine:
         t1 = time.perf_counter()
         done_seqs = [s for s, d in zip(batch, done) if d]
         dparams = self._params_of_running()
-        if getattr(dparams, "all_greedy", False) and all(s.params.greedy for s in done_seqs):
+        if getattr(dparams, "all_greedy", False) and not any(self.r_sampler[s.row] for s in done_seqs):
             params = _ALL_GREEDY
         else:
             params = _ParamsList([s.params for s in self.running] + [s.params for s in done_seqs])
         logits = self._launch(KIND_EAGER, T, nt, nl, part, nparts, 0,
                               greedy=getattr(params, "all_greedy", False))
-        toks = self._sample(logits, params, lambda: self._gen_index(rows, done_seqs)).cpu().numpy().astype(np.int64)
+        toks = self._sample(logits, params, lambda: self._gen_index(rows, done_seqs),
+                            self._sample_rows(rows, done_seqs)).cpu().numpy().astype(np.int64)
+        lp = self._take_lp()
         t2 = time.perf_counter()
         self.stats["mixed_steps"] += 1
         self.stats["decode_tokens"] += B
         self.stats["prefill_tokens"] += T - B
-        d_out = self._decode_finish(rows, toks[:B])
-        p_out = self._prefill_finish(batch, p_ctx, done, toks[B:].tolist())
+        d_out = self._decode_finish(rows, toks[:B], lp)
+        p_out = self._prefill_finish(batch, p_ctx, done, toks[B:].tolist(), lp, B)
         self.stats["mixed_host_us"] += int(1e6 * (t1 - t0 + time.perf_counter() - t2))
         self.stats["mixed_device_us"] += int(1e6 * (t2 - t1))
         if not p_out:
             return d_out
-        p = StepBatch.from_list(p_out)
-        reasons = dict(d_out.reasons)
-        reasons.update(p.reasons)
-        return StepBatch(np.concatenate([d_out.seq_ids, p.seq_ids]), np.concatenate([d_out.tokens, p.tokens]),
-                         np.concatenate([d_out.fin, p.fin]), reasons)
+        return StepBatch.concat(d_out, StepBatch.from_list(p_out))
 
     # ------------------------------------------------- async scheduling --
     # Step t+1 is built from the scheduler state as it stands after step t's LAUNCH: every
@@ -799,11 +893,7 @@ class Engine:
                 p = self._prefill_step()
                 if p is not None and len(p):
                     self._decode_since_prefill = 0
-                    reasons = dict(out.reasons)
-                    reasons.update(p.reasons)
-                    out = StepBatch(np.concatenate([out.seq_ids, p.seq_ids]), np.concatenate([out.tokens, p.tokens]),
-                                    np.concatenate([out.fin, p.fin]), reasons)
-                    return "prefill", out
+                    return "prefill", StepBatch.concat(out, p)
                 if p is not None:
                     return "prefill", out
             return "idle", out
@@ -852,7 +942,7 @@ class Engine:
             T, nt, nl = self.meta.fill_mixed(rows, ctx_d, last, p_rows, chunks, p_ctx, p_toks, want_logits=done)
             part, nparts = plan_partitions(nt, self.model.n_kv, max(int(ctx_d.max()), max(p_ctx)))
             done_seqs = [s for s, d in zip(batch, done) if d]
-            if greedy and all(s.params.greedy for s in done_seqs):
+            if greedy and not any(self.r_sampler[s.row] for s in done_seqs):
                 params = _ALL_GREEDY
             else:
                 params = _ParamsList([s.params for s in self.running] + [s.params for s in done_seqs])
@@ -877,17 +967,33 @@ class Engine:
         logits = self._launch(*launch, greedy=greedy)
         if launch[0] == KIND_GRAPH:
             logits = logits[:B]
-        toks_d = self._sample(logits, params, lambda: self._gen_index(rows, done_seqs))
+        snap_rows = self._sample_rows(rows, done_seqs)
+        toks_d = self._sample(logits, params, lambda: self._gen_index(rows, done_seqs), snap_rows)
         n = int(toks_d.shape[0])
         toks_h = self._toks_h[self._toks_flip][:n]
+        lp_d, self._last_lp = self._last_lp, None
+        lp_h = None
+        if lp_d is not None:  # log-probabilities ride back beside the tokens, behind the same event
+            if self._lp_h is None:
+                size, pin = self.meta.max_tokens * (1 + MAX_LOGPROBS), self.device.type == "cuda"
+                self._lp_h = [(torch.zeros(size, dtype=torch.float32, pin_memory=pin),
+                               torch.zeros(size, dtype=torch.int32, pin_memory=pin)) for _ in range(2)]
+            w = lp_d[0].shape[1]
+            lp_h = tuple(h[:n * w].view(n, w) for h in self._lp_h[self._toks_flip])
         self._toks_flip ^= 1
         ev = None
         if self.device.type == "cuda":
             toks_h.copy_(toks_d, non_blocking=True)
+            if lp_h is not None:
+                lp_h[0].copy_(lp_d[0], non_blocking=True)
+                lp_h[1].copy_(lp_d[1], non_blocking=True)
             ev = torch.cuda.Event()
             ev.record()
         else:
             toks_h.copy_(toks_d)
+            if lp_h is not None:
+                lp_h[0].copy_(lp_d[0])
+                lp_h[1].copy_(lp_d[1])
         # advance what does not depend on token values: decode rows gained a token (pending)
         seqs_d = list(self.running)  # aligned with rows (_decode_rows synced them)
         self.r_len[rows] += 1
@@ -904,9 +1010,9 @@ class Engine:
         else:
             self.stats["eager_decode_steps"] += 1
             self.stats["decode_steps"] += 1
-        snap_rows = np.concatenate([rows, np.asarray([s.row for s in done_seqs], dtype=rows.dtype)])
         pend = {"rows": snap_rows, "epochs": self.r_epoch[snap_rows].copy(), "seqs": seqs_d + done_seqs,
-                "toks_d": toks_d, "toks_h": toks_h, "ev": ev, "retire": set()}
+                "toks_d": toks_d, "toks_h": toks_h, "ev": ev, "retire": set(),
+                "lp": None if lp_h is None else (lp_h[0], lp_h[1], self.r_want[snap_rows].copy())}
         self._retire_by_length(pend)
         self.stats["async_host_us"] += int(1e6 * (t1 - t0 + time.perf_counter() - t1))
         return pend
@@ -959,15 +1065,21 @@ class Engine:
         rows = pend["rows"]
         n = len(rows)
         toks = pend["toks_h"][:n].numpy().copy() if n else np.zeros(0, np.int64)
+        lp = pend["lp"]
+        if lp is not None:
+            lp = (lp[0].numpy().copy(), lp[1].numpy().copy(), lp[2])
         alive = self.r_epoch[rows] == pend["epochs"]
         if not alive.all():
             ai = np.nonzero(alive)[0]
             rows, toks = rows[ai], toks[ai]
             seqs = [pend["seqs"][i] for i in ai.tolist()]
+            if lp is not None:  # a released row's log-probabilities go with its token
+                lp = tuple(a[ai] for a in lp)
         else:
             seqs = pend["seqs"]
         if not len(rows):
             return StepBatch.from_list([])
+        lps = self._deliver_lp(seqs, lp, lp[2]) if lp is not None else None
         now = time.perf_counter()
         for s in seqs:
             if s.first_token_time is None:
@@ -1001,7 +1113,7 @@ class Engine:
             for s in done:
                 self._finish(s, reasons[s.seq_id])
         self.stats["async_host_us"] += int(1e6 * (time.perf_counter() - t0))
-        return StepBatch(sids, toks, fin, reasons)
+        return StepBatch(sids, toks, fin, reasons, lps)
 
     # ----------------------------------------------------------- decode --
     def _decode_rows(self):
@@ -1076,11 +1188,12 @@ class Engine:
             t1 = time.perf_counter()
             logits = self._launch(KIND_EAGER, B, B, B, part, nparts, 0, greedy=greedy)
             self.stats["eager_decode_steps"] += 1
-        toks = self._sample(logits, params, lambda: self._gen_index(rows, ())).cpu().numpy().astype(np.int64)
+        toks = self._sample(logits, params, lambda: self._gen_index(rows, ()), rows).cpu().numpy().astype(np.int64)
+        lp = self._take_lp()
         t2 = time.perf_counter()
         self.stats["decode_steps"] += 1
         self.stats["decode_tokens"] += B
-        outs = self._decode_finish(rows, toks)
+        outs = self._decode_finish(rows, toks, lp)
         t3 = time.perf_counter()
         # host-side cost accounting (us): prep before launch, device (launch..tokens), bookkeeping
         self.stats["decode_host_prep_us"] += int(1e6 * (t1 - t0))
@@ -1088,7 +1201,17 @@ class Engine:
         self.stats["decode_host_post_us"] += int(1e6 * (t3 - t2))
         return outs
 
-    def _decode_finish(self, rows, toks) -> StepBatch:
+    def _deliver_lp(self, seqs, lp, want) -> dict | None:
+        """A step's log-probabilities onto the sequences that asked (``seqs`` aligned with the
+        leading rows of ``lp``); returns seq_id -> entry for the step's StepBatch."""
+        lps = {}
+        for i in np.nonzero(want[:len(seqs)] >= 0)[0].tolist():
+            entry = self._lp_entry(lp[0], lp[1], i, int(want[i]))
+            seqs[i].logprobs.append(entry)
+            lps[seqs[i].seq_id] = entry
+        return lps or None
+
+    def _decode_finish(self, rows, toks, lp=None) -> StepBatch:
         """Vectorised bookkeeping of one decode token per running row."""
         self.r_len[rows] += 1
         self.r_gen[rows] += 1
@@ -1105,6 +1228,7 @@ class Engine:
         fin = fin_stop | fin_len
         # one token onto every running sequence's output list, at C speed
         collections.deque(map(list.append, self._outs, toks.tolist()), maxlen=0)
+        lps = self._deliver_lp(run, lp, self.r_want[rows]) if lp is not None else None
         sids = self.r_sid[rows].copy()
         reasons = {}
         fi = np.nonzero(fin)[0]
@@ -1123,7 +1247,7 @@ class Engine:
             self._rows = rows[keep]
             for s in done:
                 self._finish(s, reasons[s.seq_id])
-        return StepBatch(sids, toks, fin, reasons)
+        return StepBatch(sids, toks, fin, reasons, lps)
 
     def _append(self, s: Sequence, tok: int) -> StepOutput:
         s.output.append(int(tok))
@@ -1226,8 +1350,24 @@ class Engine:
         best = allp[:, :, 0].argmax(dim=1)  # first max: the lowest rank = the lowest vocab index
         return _Tokens(allp[torch.arange(allp.shape[0], device=allp.device), best, 1].to(torch.int64))
 
-    def _sample(self, out, params, gen_index=None):
-        return out.ids if isinstance(out, _Tokens) else self.sampler(out, params, gen_index)
+    def _sample(self, out, params, gen_index=None, rows=None):
+        """Tokens of a step's logits rows.  ``rows``: the engine rows they belong to, in order; a
+        row with a penalty or log-probabilities takes the sampler's extended path, whose
+        log-probability tensors are left in ``self._last_lp`` for the caller to read back."""
+        self._last_lp = None
+        if isinstance(out, _Tokens):
+            return out.ids
+        if rows is not None and not getattr(params, "all_greedy", False):
+            ext = self._ext_of(np.asarray(rows, dtype=np.int64))
+            if ext is not None:
+                toks, lp, ids = self.sampler.sample_ext(out, params, ext, gen_index)
+                self._last_lp = None if lp is None else (lp, ids)
+                return toks
+        return self.sampler(out, params, gen_index)
+
+    def _sample_rows(self, rows, done_seqs):
+        """Engine rows of a step's logits rows: the decode rows, then the completed prompts."""
+        return np.concatenate([rows, np.asarray([s.row for s in done_seqs], dtype=rows.dtype)])
 
     def _gen_index(self, rows, done_seqs):
         """Output position of each row's draw (seeded sampling): decode rows' generated count

@@ -25,6 +25,11 @@ numbers):
      code)] from every rank; rank 0 completes the HTTP futures / stream queues, fails the
      requests a rank could not admit, and keeps the load table.
 
+Request records carry the repetition / presence / frequency penalties (each rank's engine keeps
+its own count table); ``logprobs`` are NOT served over this control plane (an output row is four
+int64 words): rank 0 rejects such a request with a 400 before any rank sees it
+(``check_ep_request``).
+
 All ranks therefore call ``engine.step()`` the same number of times, in lock-step, which the
 EP exchange requires.  An idle group keeps a heartbeat (one empty iteration per second) so a
 dead rank is noticed (every exchange has a deadline).  Reference contract: one predictor per
@@ -65,18 +70,20 @@ def _i2f(i: int) -> float:
 
 def packed_words(prompt, params) -> int:
     """int64 words one request record takes in ``_pack``."""
-    return 11 + len(params.stop_token_ids) + len(prompt)
+    return 14 + len(params.stop_token_ids) + len(prompt)
 
 
 def _pack(new) -> torch.Tensor:
     """[(rid, rank, prompt, SamplingParams)] -> one int64 tensor of records:
     rid, rank, len(prompt), max_tokens, top_k, ignore_eos, len(stop), has_seed, seed,
-    temperature bits, top_p bits, *stop_token_ids, *prompt."""
+    temperature bits, top_p bits, repetition / presence / frequency penalty bits, *stop_token_ids,
+    *prompt.  (No ``logprobs``: rank 0 rejects them, ``check_ep_request``.)"""
     out = []
     for rid, r, prompt, p in new:
         stop = list(p.stop_token_ids)
         out += [rid, r, len(prompt), int(p.max_tokens), int(p.top_k), int(bool(p.ignore_eos)), len(stop),
-                int(p.seed is not None), int(p.seed or 0), _f2i(p.temperature), _f2i(p.top_p), *stop, *prompt]
+                int(p.seed is not None), int(p.seed or 0), _f2i(p.temperature), _f2i(p.top_p),
+                _f2i(p.repetition_penalty), _f2i(p.presence_penalty), _f2i(p.frequency_penalty), *stop, *prompt]
     return torch.tensor(out, dtype=torch.int64)
 
 
@@ -84,16 +91,26 @@ def _unpack(buf: torch.Tensor, n: int):
     v = buf.tolist()
     i, out = 0, []
     for _ in range(n):
-        rid, r, plen, mt, tk, ign, nstop, hs, seed, tb, pb = v[i:i + 11]
-        i += 11
+        rid, r, plen, mt, tk, ign, nstop, hs, seed, tb, pb, rb, prb, fb = v[i:i + 14]
+        i += 14
         stop = v[i:i + nstop]
         i += nstop
         prompt = v[i:i + plen]
         i += plen
         out.append((rid, r, prompt, SamplingParams(max_tokens=mt, temperature=_i2f(tb), top_k=tk, top_p=_i2f(pb),
                                                    ignore_eos=bool(ign), stop_token_ids=stop,
-                                                   seed=seed if hs else None)))
+                                                   seed=seed if hs else None, repetition_penalty=_i2f(rb),
+                                                   presence_penalty=_i2f(prb), frequency_penalty=_i2f(fb))))
     return out
+
+
+def check_ep_request(params) -> None:
+    """Rank 0, before any rank sees the request: what the EP control plane cannot carry.  Its
+    output rows are four fixed int64 words (request id, token, finished, reason), so
+    log-probabilities have no way back to the HTTP front."""
+    if params is not None and params.logprobs is not None:
+        raise ValueError("logprobs are not supported by an expert-parallel (--ep) predictor: its control "
+                         "plane returns token ids only")
 
 
 class EPGroupLoop:
@@ -175,6 +192,9 @@ class EPBackend(LLMBackend):
         self.heartbeat_s = 1.0  # an idle group's empty iteration per second: a dead rank is noticed
         self.stopped = threading.Event()
 
+    def check_params(self, params) -> None:
+        check_ep_request(params)
+
     def _assign(self) -> int:
         r = min(range(len(self.load)), key=lambda i: (self.load[i], i))
         self.load[r] += 1
@@ -200,6 +220,7 @@ class EPBackend(LLMBackend):
             for i, r in enumerate(pend):
                 try:  # validated HERE, before any rank sees it: a bad request fails alone
                     self.engine.check_request(list(r.prompt), r.params)
+                    check_ep_request(r.params)
                     if packed_words(r.prompt, r.params) > self.group_loop.max_words - 2:
                         raise ValueError("request too large for the expert-parallel group's control slot")
                 except Exception as e:  # noqa: BLE001

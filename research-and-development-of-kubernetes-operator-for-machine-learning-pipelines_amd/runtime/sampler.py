@@ -1,13 +1,22 @@
-"""Token sampling (K10): greedy, temperature, top-k, top-p.
+"""Token sampling (K10): greedy, temperature, top-k, top-p, repetition / presence / frequency
+penalties and per-token log-probabilities.
 
 GPU path: the fused HIP kernel ``torch.ops.mlop.sample`` (per-row top-k select
 + softmax + top-p + inverse-CDF draw, no full-vocab sort).  Greedy batches use
 the HIP argmax directly on the LM head's bf16 logits (no fp32 copy).  CPU path: the same semantics in plain torch (oracle for tests).
+
+Penalties read a device-resident count table (one row per penalised request: bit 31 = the id is
+in the prompt, bits 0..30 = its count in the output so far), updated on the device right after
+every draw, so a draw launched one step ahead of the host still sees the previous token
+(``torch.ops.mlop.apply_penalties`` / ``penalty_update`` / ``penalty_reset``).  Log-probabilities
+are the log-softmax of the logits as the model emitted them (before penalties, temperature and
+truncation), by ``torch.ops.mlop.token_logprobs`` straight from the bf16 rows.
 """
 from __future__ import annotations
 
 from dataclasses import dataclass, field
 
+import numpy as np
 import torch
 
 from .. import ops
@@ -16,6 +25,7 @@ I32_MAX = 2**31 - 1
 # stop ids per request: bounded so every backend (single GPU, TP, the EP group's fixed control
 # slot, ep_serving.py) accepts and rejects the same requests
 MAX_STOP_IDS = 256
+MAX_LOGPROBS = 20  # top-N alternatives per token (sampling_ext.hip kLpMax)
 
 
 @dataclass
@@ -27,10 +37,23 @@ class SamplingParams:
     ignore_eos: bool = False
     stop_token_ids: list = field(default_factory=list)
     seed: int | None = None
+    repetition_penalty: float = 1.0   # HF semantics: seen logits / r if > 0 else * r
+    presence_penalty: float = 0.0     # subtracted once from every id generated so far
+    frequency_penalty: float = 0.0    # subtracted per occurrence in the output so far
+    logprobs: int | None = None       # None: off; N: the token's logprob + the top N alternatives
 
     @property
     def greedy(self) -> bool:
         return self.temperature <= 0.0
+
+    @property
+    def penalised(self) -> bool:
+        return self.repetition_penalty != 1.0 or self.presence_penalty != 0.0 or self.frequency_penalty != 0.0
+
+    @property
+    def extended(self) -> bool:
+        """Needs the sampler's extended path (count-table slot and / or log-probabilities)."""
+        return self.logprobs is not None or self.penalised
 
     def validate(self) -> "SamplingParams":
         """Raise ValueError for parameters no sampler can honour (a bad request fails alone)."""
@@ -55,6 +78,16 @@ class SamplingParams:
             raise ValueError(f"stop_token_ids must be ints in [0, {I32_MAX}]")
         if self.seed is not None and (not isinstance(self.seed, int) or not 0 <= self.seed < 2**63):
             raise ValueError("seed must be an int in [0, 2**63)")
+        r = self.repetition_penalty
+        if isinstance(r, bool) or not isinstance(r, (int, float)) or not math.isfinite(r) or r <= 0:
+            raise ValueError(f"repetition_penalty must be finite and > 0, got {r}")
+        for name in ("presence_penalty", "frequency_penalty"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or not -2.0 <= v <= 2.0:
+                raise ValueError(f"{name} must be finite and in [-2, 2], got {v}")
+        n = self.logprobs
+        if n is not None and (isinstance(n, bool) or not isinstance(n, int) or not 0 <= n <= MAX_LOGPROBS):
+            raise ValueError(f"logprobs must be None or an int in [0, {MAX_LOGPROBS}], got {n}")
         return self
 
 
@@ -132,11 +165,100 @@ def sample_reference(logits: torch.Tensor, temps: torch.Tensor, top_k: torch.Ten
     return out
 
 
+def penalties_reference(logits: torch.Tensor, table: torch.Tensor, slots, rep, freq, pres) -> torch.Tensor:
+    """Plain-torch ``apply_penalties`` (sampling_ext.hip), in place on fp32 ``logits`` [n, V].
+    Row i with slots[i] >= 0 reads table row slots[i] (bit 31 = in the prompt, bits 0..30 = count
+    c in the output); on every seen id (word != 0), in this order: l = l / r if l > 0 else l * r
+    (r != 1); l -= f * c; l -= p if c > 0."""
+    assert logits.dtype == torch.float32
+    V = logits.shape[1]
+    for i, s in enumerate(torch.as_tensor(slots).tolist()):
+        if s < 0:
+            continue
+        w = table[s, :V]
+        seen = w != 0
+        c = (w & 0x7FFFFFFF).to(torch.float32)
+        r = torch.tensor(float(rep[i]), dtype=torch.float32)
+        f = torch.tensor(float(freq[i]), dtype=torch.float32)
+        p = torch.tensor(float(pres[i]), dtype=torch.float32)
+        l = logits[i]
+        if float(r) != 1.0:
+            l = torch.where(seen, torch.where(l > 0, l / r, l * r), l)
+        l = torch.where(seen, l - f * c, l)
+        l = torch.where(c > 0, l - p, l)
+        logits[i] = l
+    return logits
+
+
+def logprobs_reference(out_lp: torch.Tensor, out_id: torch.Tensor, logits: torch.Tensor, chosen, want) -> None:
+    """Plain-torch ``token_logprobs``: row i with want[i] = N >= 0 gets the fp32 log-softmax of
+    its (unpenalised) logits at chosen[i] in column 0 and the N largest entries in columns
+    1..N, value descending, ties by lower id (a stable sort)."""
+    for i, n in enumerate(torch.as_tensor(want).tolist()):
+        if n < 0:
+            continue
+        lp = torch.log_softmax(logits[i].float(), dim=-1)
+        c = int(chosen[i])
+        out_lp[i, 0], out_id[i, 0] = lp[c], c
+        n = min(n, out_lp.shape[1] - 1, lp.numel())
+        if n:
+            order = torch.sort(-logits[i].float(), stable=True).indices[:n]
+            out_lp[i, 1:1 + n] = lp[order]
+            out_id[i, 1:1 + n] = order.to(out_id.dtype)
+
+
+class SamplerExt:
+    """What the extended path needs besides the rows' SamplingParams: the count table and, per
+    row of the logits, the table slot (-1: no penalty), the three penalties and the number of
+    top log-probabilities wanted (-1: none)."""
+
+    __slots__ = ("table", "slots", "rep", "freq", "pres", "want", "vocab")
+
+    def __init__(self, table, slots, rep, freq, pres, want, vocab=None):
+        self.table, self.vocab = table, vocab
+        self.slots = np.ascontiguousarray(slots, dtype=np.int32)
+        self.rep = np.ascontiguousarray(rep, dtype=np.float32)
+        self.freq = np.ascontiguousarray(freq, dtype=np.float32)
+        self.pres = np.ascontiguousarray(pres, dtype=np.float32)
+        self.want = np.ascontiguousarray(want, dtype=np.int32)
+
+
 class Sampler:
     def __init__(self, device, seed: int = 0):
         self.device = torch.device(device)
         self.gen = torch.Generator(device=self.device)
         self.gen.manual_seed(seed)
+
+    def sample_ext(self, logits: torch.Tensor, params, ext: SamplerExt, gen_index=None):
+        """Draw with penalties and / or log-probabilities: (tokens int64 [n], lp f32 [n, 1 + N] or
+        None, ids int32 [n, 1 + N] or None), N = the largest ``want`` of the batch.  fp32 copy ->
+        ``apply_penalties`` -> the plain draw on the penalised rows -> ``penalty_update`` ->
+        ``token_logprobs`` on the ORIGINAL logits.  Rows without a slot draw from untouched rows, so
+        they get the tokens the plain path gives them."""
+        n = logits.shape[0]
+        dev = logits.device
+
+        def put(a):
+            return torch.from_numpy(a).to(dev, non_blocking=True)
+
+        penalised = bool((ext.slots >= 0).any())
+        if penalised:
+            work = logits.float()
+            if work.data_ptr() == logits.data_ptr():
+                work = work.clone()  # never the caller's tensor
+            slots_d = put(ext.slots)
+            ops.apply_penalties(work, ext.table, slots_d, put(ext.rep), put(ext.freq), put(ext.pres))
+            toks = self(work, params, gen_index)
+            ops.penalty_update(ext.table, slots_d, toks, ext.vocab)
+        else:
+            toks = self(logits, params, gen_index)
+        nmax = int(ext.want.max()) if n else -1
+        if nmax < 0:
+            return toks, None, None
+        lp = torch.zeros(n, 1 + nmax, dtype=torch.float32, device=dev)
+        ids = torch.zeros(n, 1 + nmax, dtype=torch.int32, device=dev)
+        ops.token_logprobs(lp, ids, logits, toks, put(ext.want))
+        return toks, lp, ids
 
     def __call__(self, logits: torch.Tensor, params: list[SamplingParams], gen_index=None) -> torch.Tensor:
         """``gen_index``: per row, the position of this draw in its request's output (array, or a

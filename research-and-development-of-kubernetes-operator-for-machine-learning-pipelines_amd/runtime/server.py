@@ -124,11 +124,32 @@ _DT_NAME = {np.dtype(v): k for k, v in _DT.items()}
 
 
 def _params(p: dict) -> SamplingParams:
+    lp = p.get("logprobs")
+    if lp is not None and (isinstance(lp, bool) or not isinstance(lp, int)):
+        raise ValueError(f"logprobs must be an int, got {lp!r}")
     return SamplingParams(max_tokens=int(p.get("max_tokens", 64)), temperature=float(p.get("temperature", 0.0)),
                           top_k=int(p.get("top_k", 0)), top_p=float(p.get("top_p", 1.0)),
                           ignore_eos=bool(p.get("ignore_eos", False)),
                           stop_token_ids=list(p.get("stop_token_ids", [])),
-                          seed=None if p.get("seed") is None else int(p["seed"]))
+                          seed=None if p.get("seed") is None else int(p["seed"]),
+                          repetition_penalty=float(p.get("repetition_penalty", 1.0)),
+                          presence_penalty=float(p.get("presence_penalty", 0.0)),
+                          frequency_penalty=float(p.get("frequency_penalty", 0.0)),
+                          logprobs=lp).validate()
+
+
+def _logprob_outputs(res: dict, n: int) -> list:
+    """V2 output tensors of a request's log-probabilities: ``logprobs`` FP32 [T] and, for n > 0,
+    ``top_logprob_ids`` INT64 [T, n] / ``top_logprobs`` FP32 [T, n]."""
+    lps = res["logprobs"]
+    T = len(lps)
+    outs = [{"name": "logprobs", "shape": [T], "datatype": "FP32", "data": [e["logprob"] for e in lps]}]
+    if n > 0:
+        outs.append({"name": "top_logprob_ids", "shape": [T, n], "datatype": "INT64",
+                     "data": [t[0] for e in lps for t in e["top"]]})
+        outs.append({"name": "top_logprobs", "shape": [T, n], "datatype": "FP32",
+                     "data": [t[1] for e in lps for t in e["top"]]})
+    return outs
 
 
 def make_app(backend, metrics, version: str = "1", inject_latency_s: float | None = None,
@@ -166,6 +187,15 @@ def make_app(backend, metrics, version: str = "1", inject_latency_s: float | Non
 
     app = web.Application(middlewares=[timing], client_max_size=64 * 2**20)
 
+    def req_params(p: dict) -> SamplingParams:
+        """Parsed and validated sampling parameters (ValueError -> 400), including what this
+        backend cannot serve (an expert-parallel predictor: no log-probabilities)."""
+        params = _params(p)
+        check = getattr(backend, "check_params", None)
+        if check is not None:
+            check(params)
+        return params
+
     async def live(_):
         return web.json_response({"live": True})
 
@@ -196,7 +226,7 @@ def make_app(backend, metrics, version: str = "1", inject_latency_s: float | Non
             return web.json_response({"model_name": backend.name, "model_version": version,
                                       "id": body.get("id", ""), "outputs": [
                                           {"name": "predict", "shape": list(y.shape), "datatype": dt, "data": data}]})
-        params = _params(body.get("parameters", {}))
+        params = req_params(body.get("parameters", {}))
         if "input_ids" in inputs:
             ids = [int(v) for v in inputs["input_ids"]["data"]]
             res = await backend.generate(ids, params)
@@ -207,28 +237,33 @@ def make_app(backend, metrics, version: str = "1", inject_latency_s: float | Non
             res = await backend.generate(backend.tokenizer.encode(text), params)
             out = {"name": "text_output", "shape": [1], "datatype": "BYTES",
                    "data": [backend.tokenizer.decode(res["output_ids"])]}
+        outs = [out]
+        if params.logprobs is not None:
+            outs += _logprob_outputs(res, params.logprobs)
         return web.json_response({"model_name": backend.name, "model_version": version, "id": body.get("id", ""),
-                                  "outputs": [out], "parameters": {"finish_reason": res["finish_reason"]}})
+                                  "outputs": outs, "parameters": {"finish_reason": res["finish_reason"]}})
 
     async def generate(req):
         if backend.kind != "llm":
             raise web.HTTPBadRequest(text="generate is only served by LLM predictors")
         body = await req.json()
-        params = _params(body.get("parameters", body))
+        params = req_params(body.get("parameters", body))
         ids = body["input_ids"] if "input_ids" in body else backend.tokenizer.encode(body.get("text_input", ""))
         res = await backend.generate(ids, params)
-        return web.json_response({"model_name": backend.name, "model_version": version,
-                                  "text_output": backend.tokenizer.decode(res["output_ids"]),
-                                  "output_ids": res["output_ids"], "finish_reason": res["finish_reason"],
-                                  "usage": {"prompt_tokens": res["prompt_tokens"],
-                                            "completion_tokens": len(res["output_ids"])},
-                                  "ttft_s": res["ttft"], "latency_s": res["latency"]})
+        out = {"model_name": backend.name, "model_version": version,
+               "text_output": backend.tokenizer.decode(res["output_ids"]),
+               "output_ids": res["output_ids"], "finish_reason": res["finish_reason"],
+               "usage": {"prompt_tokens": res["prompt_tokens"], "completion_tokens": len(res["output_ids"])},
+               "ttft_s": res["ttft"], "latency_s": res["latency"]}
+        if params.logprobs is not None:  # one entry per completion token
+            out["logprobs"] = res["logprobs"]
+        return web.json_response(out)
 
     async def generate_stream(req):
         if backend.kind != "llm":
             raise web.HTTPBadRequest(text="generate_stream is only served by LLM predictors")
         body = await req.json()
-        params = _params(body.get("parameters", body))
+        params = req_params(body.get("parameters", body))
         ids = body["input_ids"] if "input_ids" in body else backend.tokenizer.encode(body.get("text_input", ""))
         r = backend.submit(ids, params, stream=True)
         resp = web.StreamResponse(headers={"Content-Type": "text/event-stream"})
@@ -237,7 +272,12 @@ def make_app(backend, metrics, version: str = "1", inject_latency_s: float | Non
             tok = await r.queue.get()
             if tok is None:
                 break
-            await resp.write(f"data: {json.dumps({'token_id': tok, 'text_output': backend.tokenizer.decode([tok])})}\n\n".encode())
+            extra = {}
+            if isinstance(tok, tuple):  # (token, logprob, top): the request asked for log-probabilities
+                tok, lp, top = tok
+                extra = {"logprob": lp, "top_logprobs": [list(t) for t in top]}
+            ev = {"token_id": tok, "text_output": backend.tokenizer.decode([tok]), **extra}
+            await resp.write(f"data: {json.dumps(ev)}\n\n".encode())
         res = await r.future
         await resp.write(f"data: {json.dumps({'finish_reason': res['finish_reason'], 'done': True})}\n\n".encode())
         await resp.write_eof()
