@@ -31,6 +31,9 @@ class ModelConfig:
     # further end-of-sequence ids (HF eos_token_id lists, e.g. Llama-3.1-Instruct's
     # [128001, 128008, 128009]: <|eot_id|> must stop generation too)
     extra_eos_ids: tuple = field(default=(), hash=False, compare=False)
+    # sliding-window attention (Mistral): the query at position i attends the keys
+    # i - W < j <= i on every layer; 0 = full causal attention
+    sliding_window: int = 0
 
     @property
     def eos_ids(self) -> tuple:
@@ -98,6 +101,13 @@ MIXTRAL_8X7B = ModelConfig(
     num_layers=32, num_heads=32, num_kv_heads=8, rope_theta=1e6, max_position=32768,
     num_experts=8, top_k=2, eos_token_id=2)
 
+# Mistral-7B-v0.1: public HF config.json of mistralai/Mistral-7B-v0.1 (Llama layout, 4096-token
+# sliding window over 32k positions)
+MISTRAL_7B = ModelConfig(
+    name="mistral-7b", vocab_size=32000, hidden_size=4096, intermediate_size=14336,
+    num_layers=32, num_heads=32, num_kv_heads=8, rope_theta=1e4, rms_eps=1e-5, max_position=32768,
+    eos_token_id=2, sliding_window=4096)
+
 # tiny shapes for CPU unit tests / GPU smoke (same code paths: GQA 4, head_dim 128)
 TINY_LLAMA = ModelConfig(
     name="tiny-llama", vocab_size=512, hidden_size=256, intermediate_size=512, num_layers=2,
@@ -112,7 +122,7 @@ TINY_MIXTRAL = ModelConfig(
 TINY_LLAMA_8H = replace(TINY_LLAMA, name="tiny-llama-8h", num_heads=8)
 TINY_MIXTRAL_8E = replace(TINY_MIXTRAL, name="tiny-mixtral-8e", num_experts=8)
 
-PRESETS = {c.name: c for c in (LLAMA3_8B, LLAMA3_70B, LLAMA31_8B, LLAMA31_70B, MIXTRAL_8X7B, TINY_LLAMA,
+PRESETS = {c.name: c for c in (LLAMA3_8B, LLAMA3_70B, LLAMA31_8B, LLAMA31_70B, MIXTRAL_8X7B, MISTRAL_7B, TINY_LLAMA,
                                 TINY_MIXTRAL, TINY_LLAMA_8H, TINY_MIXTRAL_8E)}
 # accepted aliases (MLflow tags / CR annotations use HF-ish names)
 ALIASES = {
@@ -121,6 +131,7 @@ ALIASES = {
     "meta-llama/Llama-3.1-8B": "llama3.1-8b", "meta-llama/Meta-Llama-3.1-8B": "llama3.1-8b",
     "meta-llama/Llama-3.1-70B": "llama3.1-70b", "meta-llama/Meta-Llama-3.1-70B": "llama3.1-70b",
     "mistralai/Mixtral-8x7B-v0.1": "mixtral-8x7b", "Mixtral-8x7B": "mixtral-8x7b",
+    "mistralai/Mistral-7B-v0.1": "mistral-7b", "Mistral-7B": "mistral-7b",
 }
 
 

@@ -3,7 +3,7 @@
 The operator hands a predictor its MLflow artifact URI (``s3://mlflow/<rel>``, reference
 ``mlflow_operator.py:125-127``).  When that artifact is reachable as a local directory
 (``file://`` URI, a plain path, or ``s3://mlflow/<rel>`` under ``MLOP_ARTIFACT_ROOT``)
-holding a Llama / Mixtral checkpoint in the HF layout, the runtime serves those weights;
+holding a Llama / Mistral / Mixtral checkpoint in the HF layout, the runtime serves those weights;
 otherwise it random-initialises the architecture named by the CR / MLflow tags (the
 benchmark configuration: no checkpoints are downloadable here).
 
@@ -77,9 +77,20 @@ def config_from_hf(d: dict, name: str | None = None) -> ModelConfig:
             raise ValueError(f"unsupported rope_scaling type {rt!r} (supported: default, llama3)")
     max_pos = int(d.get("max_position_embeddings", 8192))
     sw = d.get("sliding_window")
-    if sw is not None and d.get("use_sliding_window", True) and int(sw) < max_pos:
-        raise ValueError(f"sliding_window={sw} < max_position_embeddings={max_pos}: "
-                         "sliding-window attention is not implemented")
+    window = 0
+    if sw is not None and d.get("use_sliding_window", True) is not False and int(sw) < max_pos:
+        if arch == "LlamaForCausalLM":
+            # transformers ignores the key for this architecture: honouring it would change logits
+            raise ValueError(f"sliding_window={sw} < max_position_embeddings={max_pos}: "
+                             "sliding-window attention is not implemented for LlamaForCausalLM")
+        window = int(sw)
+    lt = d.get("layer_types")
+    if lt and len(set(lt)) > 1:
+        raise ValueError(f"layer_types mixes {sorted(set(lt))}: per-layer attention types are not supported")
+    if lt and window and set(lt) == {"full_attention"}:
+        window = 0
+    if lt and not window and set(lt) == {"sliding_attention"}:
+        raise ValueError("layer_types asks for sliding_attention without a sliding_window that applies")
     for flag in ("attention_bias", "mlp_bias"):
         if d.get(flag):
             raise ValueError(f"{flag}=true is not supported (bias tensors are not loaded)")
@@ -94,7 +105,7 @@ def config_from_hf(d: dict, name: str | None = None) -> ModelConfig:
         max_position=max_pos,
         tie_embeddings=bool(d.get("tie_word_embeddings", False)),
         num_experts=int(d.get("num_local_experts", 0) or 0), top_k=int(d.get("num_experts_per_tok", 2)),
-        rope_scaling=scaling, eos_token_id=int(eos), extra_eos_ids=eos_all[1:])
+        rope_scaling=scaling, eos_token_id=int(eos), extra_eos_ids=eos_all[1:], sliding_window=window)
 
 
 class _Tensors:

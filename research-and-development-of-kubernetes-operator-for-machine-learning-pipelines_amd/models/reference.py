@@ -45,6 +45,9 @@ def dense_logits(model, tokens) -> torch.Tensor:
     D, half = cfg.head_dim, cfg.head_dim // 2
     G = model.n_q // model.n_kv
     mask = torch.triu(torch.ones(T, T, dtype=torch.bool, device=dev), 1)
+    W = int(getattr(cfg, "sliding_window", 0) or 0)
+    if W > 0:  # query i sees the keys i - W < j <= i
+        mask |= torch.tril(torch.ones(T, T, dtype=torch.bool, device=dev), -W)
     for i, L in enumerate(model.layers):
         qkv = F.linear(x, L["qkv"].float())
         q = qkv[:, : model.n_q * D].view(T, model.n_q, D)

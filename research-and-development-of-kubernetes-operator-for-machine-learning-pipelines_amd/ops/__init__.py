@@ -164,18 +164,20 @@ def paged_attention(q, k_cache, v_cache, meta, out: torch.Tensor | None = None):
     _need_gpu()
     out = torch.empty_like(q) if out is None else out
     scale = 1.0 / math.sqrt(q.shape[-1])
+    window = getattr(meta, "window", 0)  # sliding window (keys i - W < j <= i); 0 = none
     if meta.tile_seq.numel():
         sem = getattr(meta, "part_sem", None)
         if sem is None:
             sem = _no_sem(q.device)
         torch.ops.mlop.paged_attention(out, meta.part_o, meta.part_ml, sem, q, k_cache, v_cache,
                                        meta.block_tables, meta.tile_seq, meta.tile_q0, meta.q_start,
-                                       meta.q_len, meta.ctx_len, scale, meta.part_tokens, meta.nparts)
+                                       meta.q_len, meta.ctx_len, scale, meta.part_tokens, meta.nparts,
+                                       window)
     pts = getattr(meta, "ptile_seq", None)
     if pts is not None and pts.numel():
         # prompt chunks: K7 flash prefill (128 q-rows per workgroup, K/V via LDS-DMA)
         torch.ops.mlop.flash_prefill(out, q, k_cache, v_cache, meta.block_tables, pts, meta.ptile_q0,
-                                     meta.q_start, meta.q_len, meta.ctx_len, scale)
+                                     meta.q_start, meta.q_len, meta.ctx_len, scale, window)
     return out
 
 

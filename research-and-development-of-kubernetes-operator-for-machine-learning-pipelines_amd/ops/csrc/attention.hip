@@ -29,8 +29,16 @@
 // of the glds table, cdna_hip_programming.md §5); each V byte once into the wave's LDS image
 // by LDS-DMA (the transpose needs it in LDS).
 //
+// Sliding window (Mistral; template parameter WIN, run-time `window` = W > 0): the query at
+// position i attends the keys i - W < j <= i.  A tile starts at kv_lo, the page pair holding the
+// first key its FIRST row sees: partitions, the block-table walk and the combine's slab count
+// are relative to kv_lo, and no page below it is read, not even its block-table entry (the
+// engine has given those pages back).  window == 0 launches the unwindowed instantiations.
+//
 // REQUIREMENT: the cache is zero-initialised at allocation (masked lanes multiply
-// p = 0 with whatever the unused slots hold; NaN garbage would poison O).
+// p = 0 with whatever the unused slots hold; NaN garbage would poison O).  Windowed: the same
+// holds for the pages of a tile's first visible pair (keys below the window are masked, not
+// skipped, inside it).
 #include <type_traits>
 #include <algorithm>
 
@@ -83,7 +91,14 @@ __device__ __forceinline__ bf16x8 vt_frag(uint32_t b, int d) {
 
 __device__ __forceinline__ int wid_of(unsigned t) { return __builtin_amdgcn_readfirstlane((int)(t >> 6)); }
 
-template <int G, int NT>  // NT bit 0: K / V loads non-temporal, bit 1: the output stores
+// first key position a windowed tile can see, rounded down to its page pair: the tile's first
+// query (position p0) attends p0 - window + 1 .. p0, later rows start later.  Partitions, the
+// block-table walk and the combine's slab count are all relative to it.
+__device__ __forceinline__ int window_kv_lo(int p0, int window) { return max(0, p0 - window + 1) & ~31; }
+
+// NT bit 0: K / V loads non-temporal, bit 1: the output stores.  WIN: sliding-window attention
+// (query i attends keys i - window < j <= i, window > 0); false compiles the window out.
+template <int G, int NT, bool WIN = false>
 __global__ void __launch_bounds__(256) paged_attn_kernel(
     uint16_t* __restrict__ out, float* __restrict__ part_o, float* __restrict__ part_ml,
     const uint16_t* __restrict__ q, const uint16_t* __restrict__ kc,
@@ -91,7 +106,7 @@ __global__ void __launch_bounds__(256) paged_attn_kernel(
     const int* __restrict__ tile_seq, const int* __restrict__ tile_q0,
     const int* __restrict__ q_start, const int* __restrict__ q_len,
     const int* __restrict__ ctx_len, int Hq, int Hkv, float scale_log2, int part_tokens,
-    int nparts, int num_blocks, int* __restrict__ sem) {
+    int nparts, int num_blocks, int* __restrict__ sem, int window) {
   constexpr int QT = 16 / G;
   // (3 waves per SIMD at 134 VGPRs; forcing 4 (127 VGPRs, amdgpu_waves_per_eu) measured the
   // same on every decode shape and the headline, scripts/history/r4_occ.sh)
@@ -106,14 +121,22 @@ __global__ void __launch_bounds__(256) paged_attn_kernel(
   const int tile = blockIdx.x, kvh = blockIdx.y, part = blockIdx.z;
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int s = tile_seq[tile], q0 = tile_q0[tile];
-  const int p_begin = part * part_tokens;
+  const int* bt = block_tables + (size_t)s * bt_stride;
+  int p_begin = part * part_tokens, kv_lo = 0;
+  int ql, ctx, qs;
+  if constexpr (WIN) {
+    // the window's start needs the lengths first: partitions count from kv_lo, and no block-table
+    // entry below it is read (the engine has released those pages)
+    ql = q_len[s], ctx = ctx_len[s], qs = q_start[s];
+    kv_lo = window_kv_lo(ctx - ql + q0, window);
+    p_begin += kv_lo;
+  }
   // The wave's first page pair, read as soon as the sequence id is known (clamped into the
   // row, used only if the pair exists): in the same round trip as ctx_len / q_len instead of
   // behind them, so the chain to the first K load is tile_seq -> block table -> K.
-  const int* bt = block_tables + (size_t)s * bt_stride;
   const int bt0 = 2 * ((p_begin >> 5) + wid_of(threadIdx.x));
   const int rawA = bt[min(bt0, bt_stride - 1)], rawB = bt[min(bt0 + 1, bt_stride - 1)];
-  const int ql = q_len[s], ctx = ctx_len[s], qs = q_start[s];
+  if constexpr (!WIN) ql = q_len[s], ctx = ctx_len[s], qs = q_start[s];
   const int last_q = min(q0 + QT, ql) - 1;           // last valid query of the tile
   const int kv_end = last_q >= 0 ? ctx - ql + last_q + 1 : 0;
   const int p_end = min(kv_end, p_begin + part_tokens);
@@ -220,8 +243,13 @@ __global__ void __launch_bounds__(256) paged_attn_kernel(
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int ta = tokA + i, tb = tokB + i;
-      pa[i] = (ta < p_end && ta <= pos_r) ? sa[i] * scale_log2 : -INFINITY;
-      pb[i] = (tb < p_end && tb <= pos_r) ? sb[i] * scale_log2 : -INFINITY;
+      if constexpr (WIN) {
+        pa[i] = (ta < p_end && ta <= pos_r && ta > pos_r - window) ? sa[i] * scale_log2 : -INFINITY;
+        pb[i] = (tb < p_end && tb <= pos_r && tb > pos_r - window) ? sb[i] * scale_log2 : -INFINITY;
+      } else {
+        pa[i] = (ta < p_end && ta <= pos_r) ? sa[i] * scale_log2 : -INFINITY;
+        pb[i] = (tb < p_end && tb <= pos_r) ? sb[i] * scale_log2 : -INFINITY;
+      }
       mx = fmaxf(mx, fmaxf(pa[i], pb[i]));
     }
     mx = max_x16_x32(mx);
@@ -322,7 +350,7 @@ __global__ void __launch_bounds__(256) paged_attn_kernel(
   // nvalid-1 keeps the agent acquire (this kernel runs two workgroups per CU, outside the
   // guide's fence-free table row) and reduces every slab, then re-arms the counter for
   // the next launch (the buffer is zero-initialised once).
-  const int nvalid = min(nparts, (kv_end + part_tokens - 1) / part_tokens);
+  const int nvalid = min(nparts, (kv_end - kv_lo + part_tokens - 1) / part_tokens);
   int* cnt = sem + (size_t)tile * Hkv + kvh;
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
@@ -359,20 +387,21 @@ __global__ void __launch_bounds__(256) paged_attn_kernel(
   *reinterpret_cast<u32x4*>(out + ((size_t)(qs + qi2) * Hq + head2) * kD + c) = ov;
 }
 
-template <int G>
+template <int G, bool WIN = false>
 __global__ void __launch_bounds__(256) attn_reduce_kernel(
     uint16_t* __restrict__ out, const float* __restrict__ part_o,
     const float* __restrict__ part_ml, const int* __restrict__ tile_seq,
     const int* __restrict__ tile_q0, const int* __restrict__ q_start,
     const int* __restrict__ q_len, const int* __restrict__ ctx_len, int Hq, int Hkv,
-    int part_tokens, int nparts) {
+    int part_tokens, int nparts, int window) {
   constexpr int QT = 16 / G;
   const int tile = blockIdx.x, kvh = blockIdx.y;
   const int s = tile_seq[tile], q0 = tile_q0[tile];
   const int ql = q_len[s], ctx = ctx_len[s], qs = q_start[s];
   const int last_q = min(q0 + QT, ql) - 1;
   const int kv_end = last_q >= 0 ? ctx - ql + last_q + 1 : 0;
-  const int nvalid = min(nparts, (kv_end + part_tokens - 1) / part_tokens);
+  const int kv_lo = WIN ? window_kv_lo(ctx - ql + q0, window) : 0;
+  const int nvalid = min(nparts, (kv_end - kv_lo + part_tokens - 1) / part_tokens);
   const int rr = threadIdx.x >> 4, c = (threadIdx.x & 15) * 8;
   const int qi = q0 + rr / G;
   if (qi >= ql) return;
@@ -411,19 +440,22 @@ static void launch_g(void* out, float* part_o, float* part_ml, const void* q, co
                      const void* vc, const int* bt, int bt_stride, const int* tile_seq,
                      const int* tile_q0, const int* q_start, const int* q_len, const int* ctx_len,
                      int num_tiles, int Hq, int Hkv, float scale_log2, int part_tokens, int nparts,
-                     int num_blocks, int* sem, hipStream_t st) {
+                     int num_blocks, int* sem, int window, hipStream_t st) {
   dim3 grid(num_tiles, Hkv, nparts);
   // K / V pages non-temporal (attn_kv_nt op): each is read once per step by one workgroup
   // (below 8 query tiles the default policy: batch 4 lost 0.7 % with it, batch 16 gained 1.8 %)
   const int nt = num_tiles >= 8 ? g_attn_kv_nt : 0;
   auto kern = nt == 3 ? paged_attn_kernel<G, 3> : nt ? paged_attn_kernel<G, 1> : paged_attn_kernel<G, 0>;
+  if (window > 0)  // the windowed instantiations; window 0 runs exactly the kernels above
+    kern = nt == 3 ? paged_attn_kernel<G, 3, true> : nt ? paged_attn_kernel<G, 1, true> : paged_attn_kernel<G, 0, true>;
   kern<<<grid, 256, 0, st>>>((uint16_t*)out, part_o, part_ml, (const uint16_t*)q, (const uint16_t*)kc,
                              (const uint16_t*)vc, bt, bt_stride, tile_seq, tile_q0, q_start, q_len, ctx_len,
-                             Hq, Hkv, scale_log2, part_tokens, nparts, num_blocks, sem);
+                             Hq, Hkv, scale_log2, part_tokens, nparts, num_blocks, sem, window);
   if (nparts > 1 && sem == nullptr) {
-    attn_reduce_kernel<G><<<dim3(num_tiles, Hkv), 256, 0, st>>>(
+    auto red = window > 0 ? attn_reduce_kernel<G, true> : attn_reduce_kernel<G, false>;
+    red<<<dim3(num_tiles, Hkv), 256, 0, st>>>(
         (uint16_t*)out, part_o, part_ml, tile_seq, tile_q0, q_start, q_len, ctx_len, Hq, Hkv,
-        part_tokens, nparts);
+        part_tokens, nparts, window);
   }
 }
 
@@ -432,13 +464,13 @@ void launch_paged_attention(void* out, float* part_o, float* part_ml, const void
                             const int* tile_seq, const int* tile_q0, const int* q_start,
                             const int* q_len, const int* ctx_len, int num_tiles, int Hq, int Hkv,
                             float scale_log2, int part_tokens, int nparts, int num_blocks,
-                            int* sem, hipStream_t st) {
+                            int* sem, int window, hipStream_t st) {
   if (num_tiles == 0) return;
   const int G = Hq / Hkv;
 #define MLOP_ATTN_CASE(GG)                                                                        \
   case GG:                                                                                        \
     launch_g<GG>(out, part_o, part_ml, q, kc, vc, bt, bt_stride, tile_seq, tile_q0, q_start,     \
-                 q_len, ctx_len, num_tiles, Hq, Hkv, scale_log2, part_tokens, nparts, num_blocks, sem, st);   \
+                 q_len, ctx_len, num_tiles, Hq, Hkv, scale_log2, part_tokens, nparts, num_blocks, sem, window, st); \
     break;
   switch (G) {
     MLOP_ATTN_CASE(1)
@@ -497,14 +529,15 @@ __device__ __forceinline__ uint32_t vt32_base(int lane) {
   return 256u * t + 16u * (c ^ vswz(t)) + 8u * (p & 1);
 }
 
-// one flash tile (128 q-rows of ONE kv head against its whole causal key range)
-template <int G>
+// one flash tile (128 q-rows of ONE kv head against its whole causal key range; WIN: against
+// the keys of its rows' sliding windows, the ring starting at the first pair any row can see)
+template <int G, bool WIN = false>
 __device__ __forceinline__ void flash32_item(
     uint16_t* smem, int tile, int kvh, uint16_t* __restrict__ out, const uint16_t* __restrict__ q,
     const uint16_t* __restrict__ kc, const uint16_t* __restrict__ vc, const int* __restrict__ block_tables,
     int bt_stride, const int* __restrict__ ptile_seq, const int* __restrict__ ptile_q0,
     const int* __restrict__ q_start, const int* __restrict__ q_len, const int* __restrict__ ctx_len, int Hq,
-    int Hkv, float scale_log2, int num_blocks) {
+    int Hkv, float scale_log2, int num_blocks, int window = 0) {
   constexpr int QB = 128 / G;            // query tokens per workgroup
   constexpr int STAGES = 3;
   constexpr int STAGE = 4 * kBS * kD;    // bf16 per stage: K page A | K page B | V page A | V page B
@@ -517,6 +550,10 @@ __device__ __forceinline__ void flash32_item(
   const int n_pairs = (kv_end + 31) >> 5;
   const int n_pages = (kv_end + kBS - 1) / kBS;
   const int wg_min_pos = ctx - ql + q0;
+  // windowed: the first pair with a key of the tile's FIRST row's window (later rows start
+  // later), and the last pair that can hold a key below some row's window
+  const int pp_lo = WIN ? max(0, wg_min_pos - window + 1) >> 5 : 0;
+  const int win_hi = WIN ? kv_end - 1 - window : 0;  // wg_max_pos - window
   const int col = lane & 31, h = lane >> 5;
 
   // this lane's q row (MFMA column): R = 32 wid + col
@@ -604,6 +641,19 @@ __device__ __forceinline__ void flash32_item(
         sc[r] = tok <= pos_r ? sc[r] : -INFINITY;
       }
     }
+    if constexpr (WIN) {
+      // a pair that can hold a key below some row's window.  Rows whose window starts past
+      // this pair get all -inf: mx = -inf never moves m off -1e30, every p is exp2(-inf) = 0,
+      // so l and O stay 0 (no NaN) until the row's first visible key.
+      if (pp * 32 <= win_hi) {
+        asm volatile("");
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int tok = pp * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+          sc[r] = tok > pos_r - window ? sc[r] : -INFINITY;
+        }
+      }
+    }
     float mx = fmaxf(fmaxf(sc[0], sc[1]), sc[2]);
 #pragma unroll
     for (int r = 3; r < 15; r += 2) mx = fmaxf(fmaxf(mx, sc[r]), sc[r + 1]);
@@ -686,9 +736,9 @@ __device__ __forceinline__ void flash32_item(
     }
   };
 
-  issue_pages(0, page_of(0), page_of(1));
-  if (n_pairs > 1) issue_pages(1, page_of(2), page_of(3));
-  int nxtA = page_of(4), nxtB = page_of(5);
+  issue_pages(0, page_of(2 * pp_lo), page_of(2 * pp_lo + 1));
+  if (pp_lo + 1 < n_pairs) issue_pages(1, page_of(2 * pp_lo + 2), page_of(2 * pp_lo + 3));
+  int nxtA = page_of(2 * pp_lo + 4), nxtB = page_of(2 * pp_lo + 5);
   auto pair_step = [&](auto st_tag, int pp) {
     constexpr int ST = decltype(st_tag)::value;
     if (pp + 1 < n_pairs) wait_vmcnt<4>(); else wait_vmcnt<0>();
@@ -702,7 +752,8 @@ __device__ __forceinline__ void flash32_item(
     softmax(qk(st_tag), pp, pf);
     pv(st_tag, pf);
   };
-  for (int pp = 0; pp < n_pairs; pp += STAGES) {
+  // (ring slots count from the first visited pair: pair pp sits in slot (pp - pp_lo) % 3)
+  for (int pp = pp_lo; pp < n_pairs; pp += STAGES) {
     pair_step(std::integral_constant<int, 0>{}, pp);
     if (pp + 1 < n_pairs) pair_step(std::integral_constant<int, 1>{}, pp + 1);
     if (pp + 2 < n_pairs) pair_step(std::integral_constant<int, 2>{}, pp + 2);
@@ -1082,19 +1133,21 @@ __global__ void __launch_bounds__(256, 2) flash32_stream_kernel(
 // ones.  The host's per-sequence latest-first tile order then pairs a heavy tile with its light
 // mirror on every slot (16 x 512: positions p, 15 - p, p, 15 - p), and the launch holds whole
 // rounds instead of ~2 k one-item workgroups.
-template <int G, int WPC, bool PERSIST>
+template <int G, int WPC, bool PERSIST, bool WIN = false>
 __global__ void __launch_bounds__(256, WPC) flash32_prefill_kernel(
     uint16_t* __restrict__ out, const uint16_t* __restrict__ q, const uint16_t* __restrict__ kc,
     const uint16_t* __restrict__ vc, const int* __restrict__ block_tables, int bt_stride,
     const int* __restrict__ ptile_seq, const int* __restrict__ ptile_q0,
     const int* __restrict__ q_start, const int* __restrict__ q_len,
-    const int* __restrict__ ctx_len, int Hq, int Hkv, float scale_log2, int num_blocks, int num_ptiles) {
+    const int* __restrict__ ctx_len, int Hq, int Hkv, float scale_log2, int num_blocks, int num_ptiles,
+    int window) {
+  static_assert(!(PERSIST && WIN), "the windowed kernel runs the plain grid only");
   constexpr int STAGES = 3;
   constexpr int STAGE = 4 * kBS * kD;    // bf16 per stage: K page A | K page B | V page A | V page B
   __shared__ __attribute__((aligned(256))) uint16_t smem[STAGES * STAGE];
   if constexpr (!PERSIST) {
-    flash32_item<G>(smem, blockIdx.x / Hkv, blockIdx.x % Hkv, out, q, kc, vc, block_tables, bt_stride, ptile_seq,
-                    ptile_q0, q_start, q_len, ctx_len, Hq, Hkv, scale_log2, num_blocks);
+    flash32_item<G, WIN>(smem, blockIdx.x / Hkv, blockIdx.x % Hkv, out, q, kc, vc, block_tables, bt_stride,
+                         ptile_seq, ptile_q0, q_start, q_len, ctx_len, Hq, Hkv, scale_log2, num_blocks, window);
   } else {
     const int kvh = blockIdx.x % Hkv, j = blockIdx.x / Hkv, S = gridDim.x / Hkv;
     for (int r = 0; r * S < num_ptiles; ++r) {
@@ -1138,27 +1191,34 @@ static int device_cus() {
 void launch_flash_prefill(void* out, const void* q, const void* kc, const void* vc, const int* bt,
                           int bt_stride, const int* ptile_seq, const int* ptile_q0,
                           const int* q_start, const int* q_len, const int* ctx_len, int num_ptiles,
-                          int Hq, int Hkv, float scale_log2, int num_blocks, hipStream_t st) {
+                          int Hq, int Hkv, float scale_log2, int num_blocks, int window, hipStream_t st) {
   if (num_ptiles == 0) return;
   const int slots = g_flash_persist >= 64 ? g_flash_persist / 64
                     : g_flash_persist > 0 ? std::max(1, g_flash_persist * device_cus() / Hkv) : 0;
-  const bool persist = slots > 0 && num_ptiles > slots;
+  // a window runs the plain grid whatever the two A/B switches say (no windowed variant of
+  // the persistent / stream grids)
+  const bool persist = window <= 0 && slots > 0 && num_ptiles > slots;
   dim3 grid((persist ? slots : num_ptiles) * Hkv);
   const bool stream = persist && g_flash_stream;
 #define MLOP_FLASH_CASE(GG)                                                                              \
   case GG:                                                                                               \
-    if (stream)                                                                                          \
+    if (window > 0)                                                                                      \
+      flash32_prefill_kernel<GG, 2, false, true><<<grid, 256, 0, st>>>(                                  \
+          (uint16_t*)out, (const uint16_t*)q, (const uint16_t*)kc, (const uint16_t*)vc, bt, bt_stride,   \
+          ptile_seq, ptile_q0, q_start, q_len, ctx_len, Hq, Hkv, scale_log2, num_blocks, num_ptiles,     \
+          window);                                                                                       \
+    else if (stream)                                                                                     \
       flash32_stream_kernel<GG><<<grid, 256, 0, st>>>(                                                   \
           (uint16_t*)out, (const uint16_t*)q, (const uint16_t*)kc, (const uint16_t*)vc, bt, bt_stride,   \
           ptile_seq, ptile_q0, q_start, q_len, ctx_len, Hq, Hkv, scale_log2, num_blocks, num_ptiles);    \
     else if (persist)                                                                                    \
       flash32_prefill_kernel<GG, 2, true><<<grid, 256, 0, st>>>(                                         \
           (uint16_t*)out, (const uint16_t*)q, (const uint16_t*)kc, (const uint16_t*)vc, bt, bt_stride,   \
-          ptile_seq, ptile_q0, q_start, q_len, ctx_len, Hq, Hkv, scale_log2, num_blocks, num_ptiles);    \
+          ptile_seq, ptile_q0, q_start, q_len, ctx_len, Hq, Hkv, scale_log2, num_blocks, num_ptiles, 0); \
     else                                                                                                 \
       flash32_prefill_kernel<GG, 2, false><<<grid, 256, 0, st>>>(                                        \
           (uint16_t*)out, (const uint16_t*)q, (const uint16_t*)kc, (const uint16_t*)vc, bt, bt_stride,   \
-          ptile_seq, ptile_q0, q_start, q_len, ctx_len, Hq, Hkv, scale_log2, num_blocks, num_ptiles);    \
+          ptile_seq, ptile_q0, q_start, q_len, ctx_len, Hq, Hkv, scale_log2, num_blocks, num_ptiles, 0); \
     break;
   switch (Hq / Hkv) {
     MLOP_FLASH_CASE(1)

@@ -109,7 +109,8 @@ void embedding(Tensor out, Tensor table, Tensor ids, int64_t vocab_start) {
 
 void flash_prefill(Tensor out, Tensor q, Tensor k_cache, Tensor v_cache, Tensor block_tables,
                    Tensor ptile_seq, Tensor ptile_q0, Tensor q_start, Tensor q_len, Tensor ctx_len,
-                   double scale) {
+                   double scale, int64_t window) {
+  TORCH_CHECK(window >= 0 && window < (1 << 30), "window must be >= 0 (0: no sliding window)");
   check_bf16(out, "out"); check_bf16(q, "q"); check_bf16(k_cache, "k_cache");
   check_bf16(v_cache, "v_cache");
   check_i32(block_tables, "block_tables"); check_i32(ptile_seq, "ptile_seq");
@@ -137,7 +138,7 @@ void flash_prefill(Tensor out, Tensor q, Tensor k_cache, Tensor v_cache, Tensor 
                              ptile_seq.data_ptr<int>(), ptile_q0.data_ptr<int>(),
                              q_start.data_ptr<int>(), q_len.data_ptr<int>(), ctx_len.data_ptr<int>(),
                              (int)ptile_seq.numel(), Hq, Hkv, (float)(scale * 1.4426950408889634),
-                             (int)k_cache.size(0), cur_stream());
+                             (int)k_cache.size(0), (int)window, cur_stream());
 }
 
 // Largest (tile, kv head) pair count that takes the in-launch split-KV combine: no cap (a cap of
@@ -154,7 +155,8 @@ int64_t attn_fused_max_pairs(int64_t n) {
 void paged_attention(Tensor out, Tensor part_o, Tensor part_ml, Tensor part_sem, Tensor q, Tensor k_cache,
                      Tensor v_cache, Tensor block_tables, Tensor tile_seq, Tensor tile_q0,
                      Tensor q_start, Tensor q_len, Tensor ctx_len, double scale,
-                     int64_t part_tokens, int64_t nparts) {
+                     int64_t part_tokens, int64_t nparts, int64_t window) {
+  TORCH_CHECK(window >= 0 && window < (1 << 30), "window must be >= 0 (0: no sliding window)");
   check_bf16(out, "out"); check_bf16(q, "q"); check_bf16(k_cache, "k_cache");
   check_bf16(v_cache, "v_cache");
   check_i32(block_tables, "block_tables"); check_i32(tile_seq, "tile_seq");
@@ -204,7 +206,7 @@ void paged_attention(Tensor out, Tensor part_o, Tensor part_ml, Tensor part_sem,
       v_cache.data_ptr(), block_tables.data_ptr<int>(), (int)block_tables.stride(0),
       tile_seq.data_ptr<int>(), tile_q0.data_ptr<int>(), q_start.data_ptr<int>(),
       q_len.data_ptr<int>(), ctx_len.data_ptr<int>(), num_tiles, Hq, Hkv, scale_log2,
-      (int)part_tokens, (int)nparts, (int)k_cache.size(0), sem, cur_stream());
+      (int)part_tokens, (int)nparts, (int)k_cache.size(0), sem, (int)window, cur_stream());
 }
 
 // ---- lazily backed KV arenas (vmm.hip)
@@ -1044,11 +1046,12 @@ TORCH_LIBRARY(mlop, m) {
   m.def("embedding(Tensor(a!) out, Tensor table, Tensor ids, int vocab_start) -> ()");
   m.def("gemm_ws(Tensor(a!) out, Tensor a, Tensor w, int epi, bool rs, float eps) -> bool");
   m.def("flash_prefill(Tensor(a!) out, Tensor q, Tensor k_cache, Tensor v_cache, Tensor block_tables, "
-        "Tensor ptile_seq, Tensor ptile_q0, Tensor q_start, Tensor q_len, Tensor ctx_len, float scale) -> ()");
+        "Tensor ptile_seq, Tensor ptile_q0, Tensor q_start, Tensor q_len, Tensor ctx_len, float scale, "
+        "int window=0) -> ()");
   m.def("paged_attention(Tensor(a!) out, Tensor(b!) part_o, Tensor(c!) part_ml, Tensor(d!) part_sem, Tensor q, "
         "Tensor k_cache, Tensor v_cache, Tensor block_tables, Tensor tile_seq, Tensor tile_q0, "
         "Tensor q_start, Tensor q_len, Tensor ctx_len, float scale, int part_tokens, "
-        "int nparts) -> ()");
+        "int nparts, int window=0) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(mlop, CUDA, m) {

@@ -26,7 +26,7 @@ void launch_paged_attention(void* out, float* part_o, float* part_ml, const void
                             const int* tile_seq, const int* tile_q0, const int* q_start,
                             const int* q_len, const int* ctx_len, int num_tiles, int Hq, int Hkv,
                             float scale_log2, int part_tokens, int nparts, int num_blocks,
-                            int* sem, hipStream_t st);
+                            int* sem, int window, hipStream_t st);  // window 0: causal only
 int flash_persist(int set);  // 0: one workgroup per flash item; n: persistent grid, n per CU
 int flash_stream(int set);   // 1: the persistent grid streams K / V pairs and Q across tiles
 int gemm_grouped_balance(int set);  // 1: equal row ranges per expert m-tile; 2: + the 16-row MFMA skip
@@ -35,7 +35,7 @@ int moe_mid_tok(int set);            // tokens per workgroup of the mid MoE disp
 void launch_flash_prefill(void* out, const void* q, const void* kc, const void* vc, const int* bt,
                           int bt_stride, const int* ptile_seq, const int* ptile_q0,
                           const int* q_start, const int* q_len, const int* ctx_len, int num_ptiles,
-                          int Hq, int Hkv, float scale_log2, int num_blocks, hipStream_t st);
+                          int Hq, int Hkv, float scale_log2, int num_blocks, int window, hipStream_t st);
 // QKV projection epilogue (EPI_ROPE): the GEMM's C tile is [q heads | k heads | v heads]
 // of head_dim 128; q/k are rotated (HF rotate-half, cos/sin table [max_pos, 128]) and
 // q goes to q_out [T, Hq, 128], k / v into the paged cache (k [NB, Hkv, BS, 128],

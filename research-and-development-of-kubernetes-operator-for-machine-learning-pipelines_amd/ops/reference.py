@@ -79,7 +79,10 @@ def gather_kv(k_cache, v_cache, block_table, n):
 
 
 def paged_attention(q, k_cache, v_cache, meta):
-    """Causal GQA attention of every query token of ``meta`` over its paged context."""
+    """Causal GQA attention of every query token of ``meta`` over its paged context.  With a
+    sliding window ``meta.window = W > 0`` the query at position i attends the keys
+    i - W < j <= i; pages wholly below the first query's window are not read at all."""
+    W = int(getattr(meta, "window", 0) or 0)
     out = torch.zeros_like(q)
     Hq, D = q.shape[1], q.shape[2]
     Hkv = k_cache.shape[1]
@@ -94,14 +97,20 @@ def paged_attention(q, k_cache, v_cache, meta):
     for s in sorted(live):
         if ql[s] == 0 or cl[s] == 0:
             continue
-        k, v = gather_kv(k_cache, v_cache, bt[s], cl[s])
+        # first page any query of the row can see (everything below may have been released)
+        BS = k_cache.shape[2]
+        lo = max(0, cl[s] - ql[s] - W + 1) // BS * BS if W > 0 else 0
+        k, v = gather_kv(k_cache, v_cache, bt[s][lo // BS:], cl[s] - lo)
         k = k.float().repeat_interleave(G, dim=1)  # [n, Hq, D]
         v = v.float().repeat_interleave(G, dim=1)
         qq = q[qs[s]:qs[s] + ql[s]].float()      # [ql, Hq, D]
         scores = torch.einsum("qhd,khd->hqk", qq, k) * scale
         pos = torch.arange(cl[s] - ql[s], cl[s], device=q.device)[:, None]
-        keys = torch.arange(cl[s], device=q.device)[None, :]
-        scores = scores.masked_fill((keys > pos)[None], float("-inf"))
+        keys = torch.arange(lo, cl[s], device=q.device)[None, :]
+        masked = keys > pos
+        if W > 0:
+            masked = masked | (keys <= pos - W)
+        scores = scores.masked_fill(masked[None], float("-inf"))
         p = torch.softmax(scores, dim=-1)
         out[qs[s]:qs[s] + ql[s]] = torch.einsum("hqk,khd->qhd", p, v).to(q.dtype)
     return out

@@ -44,6 +44,9 @@ class AttnMeta:
     # int32 tickets (zero-initialised, re-armed by the kernel): the last partition of a
     # split-KV (tile, kv head) combines the slabs in the same launch; None -> reduce launch
     part_sem: torch.Tensor | None = None
+    # sliding-window attention: the query at position i attends the keys i - window < j <= i
+    # (static per model); 0 = full causal attention
+    window: int = 0
 
 
 # 128-token partitions: one 32-token page pair per wave at batch 1 (256: 312 tok/s, 128: 322,
@@ -101,8 +104,9 @@ class MetaBuffers:
     and ``max_seqs`` concurrent sequences."""
 
     def __init__(self, max_tokens: int, max_seqs: int, max_blocks_per_seq: int, group: int,
-                 n_kv: int, max_model_len: int, device, flash_min_q: int = 17):
+                 n_kv: int, max_model_len: int, device, flash_min_q: int = 17, window: int = 0):
         self.device = torch.device(device)
+        self.window = int(window or 0)  # the model's sliding window, stamped into every meta()
         self.max_tokens, self.max_seqs, self.mb = max_tokens, max_seqs, max_blocks_per_seq
         self.G, self.n_kv, self.max_model_len = group, n_kv, max_model_len
         self.qt = 16 // group
@@ -195,7 +199,17 @@ class MetaBuffers:
             ptile_seq=self.view_d("ptile_seq", num_ptiles), ptile_q0=self.view_d("ptile_q0", num_ptiles),
             q_start=self.view_d("q_start"), q_len=self.view_d("q_len"), ctx_len=self.view_d("ctx_len"),
             part_tokens=part_tokens, nparts=nparts, part_o=self.part_o, part_ml=self.part_ml,
-            logits_idx=self.lidx_d[:n_logits], num_tokens=num_tokens, part_sem=self.part_sem)
+            logits_idx=self.lidx_d[:n_logits], num_tokens=num_tokens, part_sem=self.part_sem,
+            window=self.window)
+
+    def span(self, max_ctx: int, tile_tokens: int | None = None) -> int:
+        """The longest key range one tile of ``tile_tokens`` queries (default: a decode tile's)
+        can read at context ``max_ctx``: what ``plan_partitions`` splits.  With a window that is
+        the window, the rest of its first page pair and the tile's own tokens, not the context."""
+        if not self.window:
+            return max_ctx
+        qt = self.qt if tile_tokens is None else tile_tokens
+        return min(max_ctx, self.window + 31 + qt - 1)
 
     def fill(self, rows, q_lens, ctx_lens, token_ids_per_seq, want_logits=None):
         """Fill host arrays for a ragged batch.
@@ -238,6 +252,8 @@ class MetaBuffers:
                 pts_h[npt:npt + n] = row
                 ptq_h[npt:npt + n] = np.arange(n - 1, -1, -1, dtype=np.int32) * pqt  # latest first
                 self._pwork[npt:npt + n] = (cl - ql + pqt) + ptq_h[npt:npt + n]  # keys each tile reads
+                if self.window:  # ... from the pair holding its first row's window start
+                    np.minimum(self._pwork[npt:npt + n], self.window + 31 + pqt - 1, out=self._pwork[npt:npt + n])
                 max_flash_q = max(max_flash_q, ql)
                 npt += n
             else:

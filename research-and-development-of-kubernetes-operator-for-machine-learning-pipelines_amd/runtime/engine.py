@@ -178,6 +178,7 @@ class Sequence:
     finish_reason: str | None = None
     hashes: list = field(default_factory=list)  # prefix hashes of this sequence's full pages
     n_reg: int = 0                              # leading pages matched in / registered to the prefix cache
+    n_rel: int = 0                              # leading pages released below the sliding window (null page 0)
     pen_slot: int = -1                          # row of the penalty count table held while admitted
     logprobs: list = field(default_factory=list)  # per output token (logprob, [(id, logprob), ...]) when asked for
 
@@ -222,6 +223,9 @@ class EngineConfig:
     # rows of the penalty count table (int32 [penalty_slots, vocab], allocated on the first
     # penalised request): penalised requests admitted at once; further ones wait for a slot
     penalty_slots: int = 64
+    # sliding-window models: give back the KV pages that fell wholly below a sequence's window
+    # (False: keep them until the sequence ends; the A/B and debugging switch)
+    swa_release: bool = True
 
 
 @dataclass
@@ -331,7 +335,10 @@ class Engine:
         self.G = model.n_q // model.n_kv
         self.meta = MetaBuffers(max(cfg.max_num_batched_tokens, cfg.max_num_seqs),
                                 cfg.max_num_seqs + self.buckets[-1], self.max_blocks_per_seq,
-                                self.G, model.n_kv, self.max_model_len, self.device)
+                                self.G, model.n_kv, self.max_model_len, self.device,
+                                window=getattr(mc, "sliding_window", 0))
+        self.window = self.meta.window
+        self._swa = self.window > 0 and cfg.swa_release
         self.free_rows = list(range(cfg.max_num_seqs - 1, -1, -1))
         self.rows_hi = 0  # high-water row + 1: the block-table rows a step's upload / broadcast moves
         # struct-of-arrays state of running rows: the decode hot path is vectorised
@@ -342,7 +349,8 @@ class Engine:
         self.r_last = np.zeros(R, np.int64)     # last token (next decode input)
         self.r_ignore = np.zeros(R, bool)       # ignore_eos
         self.r_hasstop = np.zeros(R, bool)      # has stop_token_ids (checked in Python)
-        self.r_nblk = np.zeros(R, np.int64)     # KV pages held
+        self.r_nblk = np.zeros(R, np.int64)     # block-table entries in use (len(seq.blocks))
+        self.r_nrel = np.zeros(R, np.int64)     # leading entries released below the sliding window
         self.r_sid = np.zeros(R, np.int64)
         self.r_random = np.zeros(R, bool)       # non-greedy sampling
         # sampler extensions, set when a request takes its row (_admit_ext): the row's slot of the
@@ -377,6 +385,7 @@ class Engine:
         self.graphs: dict[int, tuple] = {}
         self.graph_pool = None
         self.stats = collections.Counter()
+        self.stats["kv_pages_released"] = 0
         # one-step-ahead (async) scheduling state: the in-flight step, its token read-back
         # buffers (two pinned, alternating) and the event after its metadata upload.  Under TP
         # only the leader schedules (workers follow the host-side headers, StepSync); under EP
@@ -516,11 +525,33 @@ class Engine:
         self.r_nblk[seq.row] = len(seq.blocks)
         return True
 
+    def _release_window(self, seq: Sequence, nxt: int) -> None:
+        """Sliding window: give back every page wholly below the pair-aligned start of the window
+        of the sequence's NEXT query (position ``nxt``: it attends nxt - W + 1 .. nxt, and the
+        kernels read from the page pair holding that first key).  Released block-table entries
+        become the null page 0; the list keeps its length.  Pages registered in the prefix
+        cache drop this reference and stay cached, as when a sequence ends.  Called while a step
+        is built: a page handed to another sequence is written by that step or a later one,
+        behind every launched step that still reads it."""
+        first = min(((max(0, nxt - self.window + 1)) & ~31) >> 4, len(seq.blocks))
+        if first <= seq.n_rel:
+            return
+        gone = [b for b in seq.blocks[seq.n_rel:first] if b]
+        if gone:
+            self.alloc.free(gone)
+            self.stats["kv_pages_released"] += len(gone)
+        seq.blocks[seq.n_rel:first] = [0] * (first - seq.n_rel)
+        self.meta.bt_h[seq.row, seq.n_rel:first] = 0
+        seq.n_rel = first
+        self.r_nrel[seq.row] = first
+
     def _release(self, seq: Sequence):
         if seq.blocks:
-            self.alloc.free(seq.blocks)
+            # (released window entries are the null page: never freed)
+            self.alloc.free([b for b in seq.blocks if b] if seq.n_rel else seq.blocks)
             seq.blocks = []
         seq.n_reg = 0
+        seq.n_rel = 0
         if seq.pen_slot >= 0:
             # the slot's pending penalty_update launches (a speculatively decoded row) are already
             # on the stream: the next owner's penalty_reset is enqueued behind them
@@ -529,6 +560,7 @@ class Engine:
         if seq.row >= 0:
             self.r_pen_slot[seq.row], self.r_want[seq.row] = -1, -1
             self.r_nblk[seq.row] = 0
+            self.r_nrel[seq.row] = 0
             self.r_epoch[seq.row] += 1  # an in-flight step's result for this row is stale
             self.free_rows.append(seq.row)
             seq.row = -1
@@ -690,6 +722,8 @@ class Engine:
             if budget <= 0:
                 break
             n = min(seq.length - seq.num_cached, budget)
+            if self._swa:  # between chunks: the pages below the next chunk's first window
+                self._release_window(seq, seq.num_cached)
             if not self._ensure_blocks(seq, seq.num_cached + n):
                 break
             batch.append(seq)
@@ -704,6 +738,8 @@ class Engine:
                 break
             if self.cfg.enable_prefix_caching:
                 self._match_prefix(seq)
+                if self._swa:  # a hit took all its pages: those below the window go straight back
+                    self._release_window(seq, seq.num_cached)
             n = min(seq.length - seq.num_cached, budget)
             if not self._ensure_blocks(seq, seq.num_cached + n):
                 self._release(seq)  # matched prefix pages back to the cache, row freed
@@ -751,7 +787,7 @@ class Engine:
         if len(seq.hashes) < full:
             prev = seq.hashes[-1] if seq.hashes else b""
             seq.hashes += prefix_hashes(seq.tokens(0, full * BLOCK_SIZE), full, len(seq.hashes), prev)
-        for i in range(seq.n_reg, full):
+        for i in range(max(seq.n_reg, seq.n_rel), full):  # (not the null entries of released pages)
             self.alloc.register(seq.blocks[i], seq.hashes[i])
         seq.n_reg = full
 
@@ -796,7 +832,7 @@ class Engine:
         toks = [s.tokens(s.num_cached, c) for s, c in zip(batch, ctx)]
         done = [c == s.length for s, c in zip(batch, ctx)]
         T, nt, nl = self.meta.fill(rows, chunks, ctx, toks, want_logits=done)
-        part, nparts = plan_partitions(nt, self.model.n_kv, max(ctx))
+        part, nparts = plan_partitions(nt, self.model.n_kv, self.meta.span(max(ctx)))
         done_params = [s.params for s, d in zip(batch, done) if d]
         logits = self._launch(KIND_EAGER, T, nt, nl, part, nparts, 0,
                               greedy=all(p.greedy and not p.extended for p in done_params))
@@ -834,7 +870,7 @@ class Engine:
         done = [c == s.length for s, c in zip(batch, p_ctx)]
         T, nt, nl = self.meta.fill_mixed(rows, ctx_d.astype(np.int32), self.r_last[rows],
                                          p_rows, chunks, p_ctx, p_toks, want_logits=done)
-        part, nparts = plan_partitions(nt, self.model.n_kv, max(int(ctx_d.max()), max(p_ctx)))
+        part, nparts = plan_partitions(nt, self.model.n_kv, self.meta.span(max(int(ctx_d.max()), max(p_ctx))))
         t1 = time.perf_counter()
         done_seqs = [s for s, d in zip(batch, done) if d]
         dparams = self._params_of_running()
@@ -940,7 +976,7 @@ class Engine:
             p_toks = [s.tokens(s.num_cached, c) for s, c in zip(batch, p_ctx)]
             done = [c == s.length for s, c in zip(batch, p_ctx)]
             T, nt, nl = self.meta.fill_mixed(rows, ctx_d, last, p_rows, chunks, p_ctx, p_toks, want_logits=done)
-            part, nparts = plan_partitions(nt, self.model.n_kv, max(int(ctx_d.max()), max(p_ctx)))
+            part, nparts = plan_partitions(nt, self.model.n_kv, self.meta.span(max(int(ctx_d.max()), max(p_ctx))))
             done_seqs = [s for s, d in zip(batch, done) if d]
             if greedy and not any(self.r_sampler[s.row] for s in done_seqs):
                 params = _ALL_GREEDY
@@ -958,7 +994,7 @@ class Engine:
                 launch = (KIND_GRAPH, bucket, bucket, bucket, 0, 0, bucket)
             else:
                 self.meta.fill_decode(rows, ctx_d, last, pad_to=B)
-                part, nparts = plan_partitions(B, self.model.n_kv, int(ctx_d.max()))
+                part, nparts = plan_partitions(B, self.model.n_kv, self.meta.span(int(ctx_d.max())))
                 launch = (KIND_EAGER, B, B, B, part, nparts, 0)
         if gather:
             self._src_h[:B].copy_(torch.from_numpy(self.r_tokidx[rows]))
@@ -1123,6 +1159,12 @@ class Engine:
         while True:
             rows = self._sync_rows()
             ctx = self.r_len[rows]
+            if self._swa:
+                # this step's query sits at ctx - 1; rows whose window start crossed a page pair
+                # (once per 32 tokens per row) give back the pages below it
+                first = (np.maximum(ctx - self.window, 0) & ~31) >> 4
+                for i in np.nonzero(first > self.r_nrel[rows])[0].tolist():
+                    self._release_window(self.running[i], int(ctx[i]) - 1)
             nblk = self.r_nblk[rows]
             want = (ctx + BLOCK_SIZE - 1) // BLOCK_SIZE
             need = np.nonzero(want > nblk)[0]
@@ -1184,7 +1226,7 @@ class Engine:
             self.stats["graph_steps"] += 1
         else:
             self.meta.fill_decode(rows, ctx, last, pad_to=B)
-            part, nparts = plan_partitions(B, self.model.n_kv, int(ctx.max()))
+            part, nparts = plan_partitions(B, self.model.n_kv, self.meta.span(int(ctx.max())))
             t1 = time.perf_counter()
             logits = self._launch(KIND_EAGER, B, B, B, part, nparts, 0, greedy=greedy)
             self.stats["eager_decode_steps"] += 1
@@ -1310,7 +1352,7 @@ class Engine:
         if eager:
             if kind == KIND_GRAPH:
                 rows, ctx, last, mctx = self._repad
-                part, nparts = plan_partitions(T, self.model.n_kv, mctx)
+                part, nparts = plan_partitions(T, self.model.n_kv, self.meta.span(mctx))
                 kind, nt, nl = KIND_EAGER, T, T
             self.model.moe_capacity_tokens = t_max
             return kind, T, nt, nl, part, nparts, 0
@@ -1424,7 +1466,7 @@ class Engine:
                 self.meta.fill_decode(empty, empty, np.zeros(0, dtype=np.int64), pad_to=b)
                 self.meta.upload(b, b)
                 m.moe_capacity_tokens = b  # EP: every rank's graph of bucket b exchanges b rows
-                part, nparts = plan_partitions(b, m.n_kv, self.max_model_len)
+                part, nparts = plan_partitions(b, m.n_kv, self.meta.span(self.max_model_len))
                 meta = self.meta.meta(b, b, b, part, nparts)
                 ids = self.meta.ids_d[:b]
                 # decode fills (fill_decode) give every row, padding included, its own logits row

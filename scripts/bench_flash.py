@@ -1,6 +1,9 @@
 """K7 flash-prefill microbench: S fresh prompts of L tokens each in ONE chunk (causal),
 Llama-3-8B GQA (32 q / 8 kv heads, D = 128), K/V already in scattered 16-token pages.
-Reports us per call and causal attention TFLOP/s (QK^T + PV, 4 * sum(pos+1) * D * Hq)."""
+Reports us per call and causal attention TFLOP/s (QK^T + PV, 4 * sum(pos+1) * D * Hq).
+--window W: sliding-window attention (each query sees its last W keys; the FLOPs counted are
+those of the visible keys, the tiles' LPT work is clamped as the engine's)."""
+import argparse
 import json
 import os
 import sys
@@ -14,6 +17,9 @@ from mlopamd import ops  # noqa: E402
 ops.load()
 dev = torch.device("cuda")
 bf = torch.bfloat16
+ap = argparse.ArgumentParser()
+ap.add_argument("--window", type=int, default=0, help="sliding window in tokens (0: full causal attention)")
+WIN = ap.parse_args().window
 S = int(os.environ.get("S", "4"))
 L = int(os.environ.get("L", "2048"))
 ITERS = int(os.environ.get("ITERS", "20"))
@@ -35,7 +41,10 @@ if os.environ.get("ORDER", "lpt") == "lpt":  # attn_meta.order_flash_tiles (the 
     from mlopamd.runtime.attn_meta import order_flash_tiles
 
     pts, ptq = np.asarray(pts, dtype=np.int32), np.asarray(ptq, dtype=np.int32)
-    order_flash_tiles(pts, ptq, (ptq + pqt).astype(np.int32))
+    work = (ptq + pqt).astype(np.int32)
+    if WIN:
+        work = np.minimum(work, WIN + 31 + pqt - 1).astype(np.int32)
+    order_flash_tiles(pts, ptq, work)
 
 
 class Meta:
@@ -49,12 +58,15 @@ m.q_start, m.q_len = d(q_start), d(np.full(S, L))
 m.tile_seq = m.tile_q0 = d(np.zeros(0))
 m.ptile_seq, m.ptile_q0 = d(pts), d(ptq)
 m.part_tokens, m.nparts = L, 1
+m.window = WIN
 m.part_o = m.part_ml = torch.empty(1, device=dev)
 kc = torch.randn(NB, Hkv, BS, D, device=dev, dtype=bf)
 vc = torch.randn(NB, Hkv, BS, D, device=dev, dtype=bf)
 q = torch.randn(S * L, Hq, D, device=dev, dtype=bf)
 out = torch.empty_like(q)
 flops = 4 * S * (L * (L + 1) // 2) * D * Hq
+if WIN:
+    flops = 4 * S * sum(min(p + 1, WIN) for p in range(L)) * D * Hq
 # PERSIST: flash_persist values to interleave (0 = one workgroup per item; n = the persistent
 # grid with n workgroups per CU; an "s" suffix runs it as the cross-tile stream, flash_stream 1),
 # e.g. "0,3,2s"
@@ -74,7 +86,7 @@ for pvs in os.environ.get("PERSIST", str(torch.ops.mlop.flash_persist(-1))).spli
         ev[1].record()
         ev[1].synchronize()
         best = min(best, ev[0].elapsed_time(ev[1]) / ITERS * 1e3)
-    line = dict(S=S, L=L, order=os.environ.get("ORDER", "lpt"), persist=pvs, tiles=len(pts), us=round(best, 1),
+    line = dict(S=S, L=L, window=WIN, order=os.environ.get("ORDER", "lpt"), persist=pvs, tiles=len(pts), us=round(best, 1),
                 tflops=round(flops / best / 1e6, 1))
     if os.environ.get("CHECK"):
         from mlopamd.ops import reference as ref
