@@ -363,6 +363,29 @@ def _nearest_choice(key):
     return best[1] if best else None
 
 
+def _fused_or_unfused(key, M, dev, applicable: bool, fused, unfused, time_fused=None, time_unfused=None):
+    """One projection that has a fused MFMA form and an unfused (GEMM + separate op) form:
+    the backend override, then the table choice, the nearest timed row count when frozen, the
+    first-use timing outside graph capture, and the record in ``_GEMM_USED``.  ``key`` is the
+    autotune key (M bucket, N, K, epilogue); the timed candidates default to the forms."""
+    if not applicable or GEMM_BACKEND == "hipblaslt":
+        return unfused()  # the GEMM inside records its own backend
+    if GEMM_BACKEND == "mlop":
+        _GEMM_USED[key] = "mlop"
+        return fused()
+    c = _GEMM_CHOICE.get(key)
+    if c is None and AUTOTUNE_FROZEN:
+        c = _nearest_choice(key)
+    if c is None and not torch.cuda.is_current_stream_capturing():
+        times = _time_candidates([("mlop", time_fused or fused), ("hipblaslt", time_unfused or unfused)], M, dev)
+        c = min(times, key=times.get)
+        _GEMM_CHOICE[key], _GEMM_TIMES[key] = c, times
+    if c in (None, "mlop"):
+        _GEMM_USED[key] = "mlop"
+        return fused()
+    return unfused()
+
+
 def gemm_add_rmsnorm(x, w, residual, norm_w, eps: float):
     """Decoder projection + residual + norm: residual <- residual + x @ w^T (bf16);
     returns rmsnorm(residual) * norm_w.  On GPU the split-K MFMA GEMM's reduce
@@ -391,25 +414,16 @@ def gemm_add_rmsnorm(x, w, residual, norm_w, eps: float):
     def unfused(res):
         return add_rmsnorm(gemm(x2, w), res, norm_w, eps)
 
-    key = (_mbucket(M), N, K, EPI_ADD_RMSNORM)
-    if nws == 0 or GEMM_BACKEND == "hipblaslt":
-        return unfused(residual)  # the GEMM inside records its own backend
-    if GEMM_BACKEND == "mlop":
-        _GEMM_USED[key] = "mlop"
-        return fused(residual)
-    c = _GEMM_CHOICE.get(key)
-    if c is None and AUTOTUNE_FROZEN:
-        c = _nearest_choice(key)
-    if c is None and not torch.cuda.is_current_stream_capturing():
-        scratch = residual.clone()
-        times = _time_candidates([("mlop", lambda: fused(scratch)), ("hipblaslt", lambda: unfused(scratch))],
-                                 M, x.device)
-        c = min(times, key=times.get)
-        _GEMM_CHOICE[key], _GEMM_TIMES[key] = c, times
-    if c in (None, "mlop"):
-        _GEMM_USED[key] = "mlop"
-        return fused(residual)
-    return unfused(residual)
+    scratch = []  # the timed candidates add into a copy of the residual, made on first use
+
+    def timed(form):
+        if not scratch:
+            scratch.append(residual.clone())
+        return form(scratch[0])
+
+    return _fused_or_unfused((_mbucket(M), N, K, EPI_ADD_RMSNORM), M, x.device, nws != 0,
+                             lambda: fused(residual), lambda: unfused(residual),
+                             lambda: timed(fused), lambda: timed(unfused))
 
 
 EPI_ROPE = 3  # QKV projection + RoPE + paged-cache stores in the GEMM epilogue
@@ -443,24 +457,10 @@ def qkv_rope_cache(x, w, positions, cos_sin, slots, k_cache, v_cache, n_q_heads:
     def unfused():
         return rope_cache(gemm(x2, w), positions, cos_sin, slots, k_cache, v_cache, n_q_heads, q_out)
 
-    key = (_mbucket(M), N, K, EPI_ROPE)
-    if GEMM_BACKEND == "hipblaslt" or not torch.ops.mlop.gemm_rope_supported(M, N, K):
-        return unfused()
-    if GEMM_BACKEND == "mlop":
-        _GEMM_USED[key] = "mlop"
-        return fused()
-    c = _GEMM_CHOICE.get(key)
-    if c is None and AUTOTUNE_FROZEN:
-        c = _nearest_choice(key)
-    if c is None and not torch.cuda.is_current_stream_capturing():
-        # fused() re-writes the same cache slots with the same values: idempotent
-        times = _time_candidates([("mlop", fused), ("hipblaslt", unfused)], M, x.device)
-        c = min(times, key=times.get)
-        _GEMM_CHOICE[key], _GEMM_TIMES[key] = c, times
-    if c in (None, "mlop"):
-        _GEMM_USED[key] = "mlop"
-        return fused()
-    return unfused()
+    # (timing fused() re-writes the same cache slots with the same values: idempotent)
+    return _fused_or_unfused((_mbucket(M), N, K, EPI_ROPE), M, x.device,
+                             GEMM_BACKEND != "hipblaslt" and bool(torch.ops.mlop.gemm_rope_supported(M, N, K)),
+                             fused, unfused)
 
 
 # ---- norm chain (large-M TP=1 decoder): the add + RMSNorm passes folded into the GEMMs ----
@@ -496,7 +496,7 @@ def norm_chain_ok(M: int, H: int, shapes, device=None, epis=None) -> bool:
     """True when the chain can run at M rows: hidden size H (ss groups of 128 columns, 16 per
     quad of lanes) and every (N, K) GEMM of the chain on the four-wave kernel, with the band
     tickets' scratch reserved on ``device`` and one ticket per 256-row band (w4_chain_ok checks
-    everything launch_w4_chain does, so the chain is decided once per forward and never refused
+    everything launch_gemm_chain does, so the chain is decided once per forward and never refused
     after a residual was updated in place).  At M <= 4 every GEMM must take the GEMV form
     instead (``epis``: each shape's epilogue, default plain)."""
     if NORM_CHAIN == "force":
@@ -506,17 +506,17 @@ def norm_chain_ok(M: int, H: int, shapes, device=None, epis=None) -> bool:
     if device is not None and torch.device(device).type != "cuda":
         return False  # the torch reference path (CPU) has no chain kernels
     _need_gpu()
-    if M <= decode_chain_max_m():
-        epis = epis or [EPI_NONE] * len(shapes)
-        return GEMV_CHAIN and all(bool(torch.ops.mlop.gemv_chain_supported(M, N, K, e))
-                                  for (N, K), e in zip(shapes, epis))
-    if device is not None and torch.device(device).type == "cuda":
+    decode = M <= decode_chain_max_m()
+    if decode and not GEMV_CHAIN:
+        return False
+    if not decode and device is not None and torch.device(device).type == "cuda":
         _sk_reserve(torch.device(device))
-    if M <= 64 and epis is not None:
-        # 5-64 rows: the planner's small tiles (O / down finish their split-K and leave the row
-        # sums of squares, gate_up / QKV scale their rows: gemm.hip mid_chain_ok)
-        return all(bool(torch.ops.mlop.mid_chain_ok(M, N, K, e)) for (N, K), e in zip(shapes, epis))
-    return all(bool(torch.ops.mlop.w4_chain_ok(M, N, K)) for N, K in shapes)
+    # one question per GEMM (gemm_plan.cc chain_ok): the decode forms up to decode_chain_max_m
+    # rows (epilogue default plain), the mid chain up to 64 rows where the epilogues are given
+    # (O / down finish their split-K and leave the row sums of squares, gate_up / QKV scale
+    # their rows), else the four-wave chain
+    epis = epis if epis is not None else [EPI_NONE if decode else -1] * len(shapes)
+    return all(bool(torch.ops.mlop.chain_ok(M, N, K, e)) for (N, K), e in zip(shapes, epis))
 
 
 def ss_buffer(M: int, H: int, device) -> torch.Tensor:

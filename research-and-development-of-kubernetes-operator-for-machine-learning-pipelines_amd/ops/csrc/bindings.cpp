@@ -14,6 +14,7 @@
 #include <cmath>
 
 #include "launch.h"
+#include "gemm_plan.h"
 
 namespace {
 
@@ -239,30 +240,100 @@ bool vmm_map_chunks(Tensor flat, int64_t region_stride, int64_t n_regions, int64
 int64_t vmm_chunks_ready(Tensor flat) { return mlop::vmm_chunks_ready(flat.data_ptr()); }
 int64_t vmm_error(Tensor flat) { return mlop::vmm_error(flat.data_ptr()); }
 
-int64_t gemm_big_variant(int64_t set) { return mlop::gemm_big_variant((int)set); }
-int64_t gemm_half_tile(int64_t set) { return mlop::gemm_half_tile((int)set); }
-int64_t gemm_small_nt(int64_t set) { return mlop::gemm_small_nt((int)set); }
-int64_t attn_kv_nt(int64_t set) { return mlop::attn_kv_nt((int)set); }
-int64_t gemm_slab_nt(int64_t set) { return mlop::gemm_slab_nt((int)set); }
-int64_t gemm_rope_split(int64_t set) { return mlop::gemm_rope_split((int)set); }
-int64_t gemm_split_target(int64_t set) { return mlop::gemm_split_target((int)set); }
-int64_t gemm_grouped_narrow(int64_t set) { return mlop::gemm_grouped_narrow((int)set); }
-int64_t moe_mid_max_tokens(int64_t set) { return mlop::moe_mid_max_tokens((int)set); }
+// the int knobs: "name(int set=-1) -> int", set >= 0 changes the value, returns the current one
+template <int (*F)(int)>
+int64_t knob(int64_t set) { return F((int)set); }
+
 void gemm_dense_plan(int64_t variant, int64_t bm, int64_t bn, int64_t splits, int64_t stages) {
   mlop::gemm_dense_plan((int)variant, (int)bm, (int)bn, (int)splits, (int)stages);
 }
 void gemm_grouped_plan(int64_t bm, int64_t bn, int64_t stages, int64_t splits) {
   mlop::gemm_grouped_plan((int)bm, (int)bn, (int)stages, (int)splits);
 }
-int64_t gemm_small_stages(int64_t set) { return mlop::gemm_small_stages((int)set); }
-int64_t gemm_small_tile(int64_t set) { return mlop::gemm_small_tile((int)set); }
-int64_t gemm_sk_mode(int64_t set) { return mlop::gemm_sk_mode((int)set); }
 bool gemm_sk_reserve() { return mlop::gemm_sk_reserve(); }
-int64_t gemm_sk_workgroups(int64_t M, int64_t N, int64_t K) { return mlop::gemm_sk_workgroups((int)M, (int)N, (int)K); }
 
+// ---- queries: views of the planner's route for the current device and knobs (gemm_plan.h) ----
+int64_t gemm_sk_workgroups(int64_t M, int64_t N, int64_t K) {
+  return mlop::gemm_sk_workgroups(mlop::gemm_live_env(), (int)M, (int)N, (int)K);
+}
 int64_t gemm_workspace(int64_t M, int64_t N, int64_t K, int64_t epi) {
-  if (epi == 2) return mlop::gemm_workspace_floats((int)M, (int)N, (int)K, 0);  // GEMM + add + RMSNorm: split-K slabs
-  return mlop::gemm_workspace_floats((int)M, (int)N, (int)K, (int)epi);
+  // epi 2 = GEMM + add + RMSNorm: the split-K slabs of the plain plan
+  return mlop::gemm_workspace_floats(mlop::gemm_live_env(), (int)M, (int)N, (int)K, epi == 2 ? 0 : (int)epi);
+}
+bool gemm_rope_supported(int64_t M, int64_t N, int64_t K) {
+  return mlop::gemm_rope_supported(mlop::gemm_live_env(), (int)M, (int)N, (int)K);
+}
+bool w4_chain_ok(int64_t M, int64_t N, int64_t K) { return mlop::w4_chain_ok(mlop::gemm_live_env(), (int)M, (int)N, (int)K); }
+bool mid_chain_ok(int64_t M, int64_t N, int64_t K, int64_t epi) {
+  return mlop::mid_chain_ok(mlop::gemm_live_env(), (int)M, (int)N, (int)K, (int)epi);
+}
+bool gemv_chain_supported(int64_t M, int64_t N, int64_t K, int64_t epi) {
+  return mlop::decode_chain_takes(mlop::gemm_live_env(), (int)M, (int)N, (int)K, (int)epi);
+}
+bool chain_ok(int64_t M, int64_t N, int64_t K, int64_t epi) {
+  return mlop::chain_ok(mlop::gemm_live_env(), (int)M, (int)N, (int)K, (int)epi);
+}
+int64_t decode_chain_max_m() { return mlop::decode_chain_max_m(mlop::gemm_live_env()); }
+
+// The route of one call as a flat int list, in gemm_plan.h's Route field order: family (0 refused, 1
+// GEMV, 2 weight-streaming, 3 LDS-DMA tile, 4 ping-pong, 5 four-wave, 6 four-wave half height), tile
+// (index into gemm_tile_configs, -1: none), BM, BN, WM, WN, stages, setprio, splits, k_chunk, m_tiles,
+// sk_d, sk_wgs, finish (0 none, 1 split-K reduce, 2 split-K add + RMSNorm, 3 RoPE-slab reduce, 4
+// RMSNorm), ws_src (0 none, 1 the caller's workspace, 2 the stream-K scratch), ws_floats.
+// op: 0 plain, 1 SiLU-mul, 2 GEMM + add + RMSNorm, 3 QKV + RoPE, 4 chain res_ss, 8 / 9 / 11 chain
+// row-scaled plain / SiLU-mul / RoPE, 16 / 17 grouped plain / SiLU-mul.
+std::vector<int64_t> route_list(const mlop::PlanEnv& env, int64_t M, int64_t N, int64_t K, int64_t op,
+                                int64_t n_groups, int64_t rows_per_group) {
+  mlop::GemmCall c;
+  c.op = (int)op, c.M = (int)M, c.N = (int)N, c.K = (int)K;
+  c.n_groups = (int)n_groups, c.rows_per_group = (int)rows_per_group;
+  long f[mlop::kRouteFields];
+  mlop::gemm_route_fields(mlop::gemm_route(env, c), f);
+  return std::vector<int64_t>(f, f + mlop::kRouteFields);
+}
+std::vector<int64_t> gemm_route(int64_t M, int64_t N, int64_t K, int64_t op, int64_t n_groups, int64_t rows_per_group) {
+  return route_list(mlop::gemm_live_env(), M, N, K, op, n_groups, rows_per_group);
+}
+// the same with the two device facts given: cus CUs, sk = the stream-K scratch reserved
+std::vector<int64_t> gemm_route_env(int64_t M, int64_t N, int64_t K, int64_t op, int64_t cus, bool sk,
+                                    int64_t n_groups, int64_t rows_per_group) {
+  mlop::PlanEnv env = mlop::gemm_knobs();
+  env.cus = (int)cus, env.sk = sk;
+  return route_list(env, M, N, K, op, n_groups, rows_per_group);
+}
+// the tile table, 7 ints per entry: BM, BN, WM, WN, stages, setprio, rope
+std::vector<int64_t> gemm_tile_configs() {
+  std::vector<int64_t> v;
+  for (const mlop::TileCfg& t : mlop::kGemmTiles) v.insert(v.end(), {t.BM, t.BN, t.WM, t.WN, t.stages, t.setprio, t.rope});
+  return v;
+}
+
+// a: bf16 [M, K] activations, unit inner stride, 16-B aligned rows
+void check_a(const Tensor& a) {
+  TORCH_CHECK(a.is_cuda() && a.scalar_type() == at::kBFloat16 && a.dim() == 2 && a.stride(1) == 1 &&
+                  a.stride(0) % 8 == 0, "a must be bf16 [M, K], 16-B aligned rows");
+}
+
+// the QKV + RoPE + paged-cache argument block of a [M, K] x w [N, K] projection
+mlop::RopeEpi rope_args(const Tensor& q_out, const Tensor& k_cache, const Tensor& v_cache, const Tensor& a,
+                        const Tensor& w, const Tensor& pos, const Tensor& cos_sin, const Tensor& slots) {
+  check_a(a);
+  check_bf16(w, "w"); check_bf16(q_out, "q_out"); check_bf16(k_cache, "k_cache");
+  check_bf16(v_cache, "v_cache"); check_i32(pos, "pos"); check_i32(slots, "slots");
+  TORCH_CHECK(cos_sin.is_cuda() && cos_sin.scalar_type() == at::kFloat && cos_sin.is_contiguous(),
+              "cos_sin f32");
+  const int64_t M = a.size(0), K = a.size(1), N = w.size(0);
+  TORCH_CHECK(w.dim() == 2 && w.size(1) == K && K % 64 == 0, "w [N, K], K % 64");
+  TORCH_CHECK(q_out.dim() == 3 && k_cache.dim() == 4 && v_cache.dim() == 4, "ranks");
+  const int64_t Hq = q_out.size(1), D = q_out.size(2), Hkv = k_cache.size(1), BS = k_cache.size(2);
+  TORCH_CHECK(D == 128 && k_cache.size(3) == D && v_cache.sizes() == k_cache.sizes(),
+              "head_dim 128; k and v [NB,Hkv,BS,D]");
+  TORCH_CHECK(N == (Hq + 2 * Hkv) * D && q_out.size(0) == M, "qkv width / q_out rows");
+  TORCH_CHECK(pos.numel() == M && slots.numel() == M, "pos/slots length");
+  TORCH_CHECK(cos_sin.dim() == 2 && cos_sin.size(1) == D, "cos_sin [max_pos, D]");
+  return mlop::RopeEpi{(uint16_t*)q_out.data_ptr(), (uint16_t*)k_cache.data_ptr(),
+                       (uint16_t*)v_cache.data_ptr(), pos.data_ptr<int>(), cos_sin.data_ptr<float>(),
+                       slots.data_ptr<int>(), (int)Hq, (int)Hkv, (int)BS};
 }
 
 // out[M, N or N/2] = epi(a[M, K] . w[N, K]^T)
@@ -297,47 +368,25 @@ void gemm(Tensor out, Tensor a, Tensor w, Tensor ws, int64_t epi) {
 // does not take the fused tiling (caller runs gemm + rope_cache)
 bool gemm_rope_cache(Tensor q_out, Tensor k_cache, Tensor v_cache, Tensor a, Tensor w, Tensor pos,
                      Tensor cos_sin, Tensor slots) {
-  TORCH_CHECK(a.is_cuda() && a.scalar_type() == at::kBFloat16 && a.dim() == 2 && a.stride(1) == 1 &&
-                  a.stride(0) % 8 == 0, "a must be bf16 [M, K], 16-B aligned rows");
-  check_bf16(w, "w"); check_bf16(q_out, "q_out"); check_bf16(k_cache, "k_cache");
-  check_bf16(v_cache, "v_cache"); check_i32(pos, "pos"); check_i32(slots, "slots");
-  TORCH_CHECK(cos_sin.is_cuda() && cos_sin.scalar_type() == at::kFloat && cos_sin.is_contiguous(),
-              "cos_sin f32");
-  const int64_t M = a.size(0), K = a.size(1), N = w.size(0);
-  TORCH_CHECK(w.dim() == 2 && w.size(1) == K && K % 64 == 0, "w [N, K], K % 64");
-  TORCH_CHECK(q_out.dim() == 3 && k_cache.dim() == 4 && v_cache.dim() == 4, "ranks");
-  const int64_t Hq = q_out.size(1), D = q_out.size(2), Hkv = k_cache.size(1), BS = k_cache.size(2);
-  TORCH_CHECK(D == 128 && k_cache.size(3) == D && v_cache.sizes() == k_cache.sizes(),
-              "head_dim 128; k and v [NB,Hkv,BS,D]");
-  TORCH_CHECK(N == (Hq + 2 * Hkv) * D && q_out.size(0) == M, "qkv width / q_out rows");
-  TORCH_CHECK(pos.numel() == M && slots.numel() == M, "pos/slots length");
-  TORCH_CHECK(cos_sin.dim() == 2 && cos_sin.size(1) == D, "cos_sin [max_pos, D]");
+  const mlop::RopeEpi re = rope_args(q_out, k_cache, v_cache, a, w, pos, cos_sin, slots);
   c10::DeviceGuard g(a.device());
-  mlop::RopeEpi re{(uint16_t*)q_out.data_ptr(), (uint16_t*)k_cache.data_ptr(),
-                   (uint16_t*)v_cache.data_ptr(), pos.data_ptr<int>(), cos_sin.data_ptr<float>(),
-                   slots.data_ptr<int>(), (int)Hq, (int)Hkv, (int)BS};
-  return mlop::launch_gemm_rope(a.data_ptr(), (int)a.stride(0), w.data_ptr(), (int)M, (int)N, (int)K,
-                                re, cur_stream());
+  return mlop::launch_gemm_rope(a.data_ptr(), (int)a.stride(0), w.data_ptr(), (int)a.size(0), (int)w.size(0),
+                                (int)a.size(1), re, cur_stream());
 }
 
-bool gemm_rope_supported(int64_t M, int64_t N, int64_t K) {
-  return mlop::gemm_rope_supported((int)M, (int)N, (int)K);
-}
-
-// ---- norm chain on the four-wave GEMM (large-M TP=1 decoder, unit norm weights) ----
-// residual [M, N] += a . w^T in place; ss (f32, M * (N / 128 + 1)) = [M, N / 128] per-row,
-// per-128-column partial sums of squares of the new residual, then the [M] row totals; false =
-// the shape does not run on the four-wave kernel
-bool w4_chain_ok_op(int64_t M, int64_t N, int64_t K) { return mlop::w4_chain_ok((int)M, (int)N, (int)K); }
-
+// ---- norm chain (TP=1 decoder, unit norm weights): launch_gemm_chain runs each GEMM on the form
+// the planner names for its row count (decode GEMV / weight-streaming, mid, four-wave) ----
+// ss (f32, M * (H / 128 + 1)) = [M, H / 128] per-row, per-128-column partial sums of squares of
+// the residual, then the [M] row totals
 static void check_ss(const Tensor& ss, int64_t M, int64_t H, const char* name) {
   TORCH_CHECK(ss.is_cuda() && ss.scalar_type() == at::kFloat && ss.is_contiguous() &&
                   ss.numel() == M * (H / 128 + 1), name, " must be f32 [M * (H / 128 + 1)] contiguous");
 }
 
+// residual [M, N] += a . w^T in place, ss_out <- the new residual's sums of squares; false = the
+// shape runs on no form of the chain
 bool gemm_res_ss(Tensor residual, Tensor a, Tensor w, Tensor ss_out) {
-  TORCH_CHECK(a.is_cuda() && a.scalar_type() == at::kBFloat16 && a.dim() == 2 && a.stride(1) == 1 &&
-                  a.stride(0) % 8 == 0, "a must be bf16 [M, K], 16-B aligned rows");
+  check_a(a);
   check_bf16(w, "w"); check_bf16(residual, "residual");
   const int64_t M = a.size(0), K = a.size(1), N = w.size(0);
   TORCH_CHECK(w.dim() == 2 && w.size(1) == K, "w [N, K]");
@@ -345,34 +394,16 @@ bool gemm_res_ss(Tensor residual, Tensor a, Tensor w, Tensor ss_out) {
                   residual.stride(0) % 8 == 0, "residual [M, N]");
   TORCH_CHECK(N % 128 == 0, "N % 128");
   check_ss(ss_out, M, N, "ss");
-  if (M <= mlop::decode_chain_max_m()) {  // decode sizes: the GEMV (M <= 4) / weight-streaming MFMA chain
-                 // (EPI_RES); its consumers take their row factors from the residual itself, so ss_out is not written
-    if (residual.stride(0) != N || !mlop::decode_chain_takes((int)M, (int)N, (int)K, 0)) return false;
-    c10::DeviceGuard g(a.device());
-    if (M <= mlop::gemv_chain_max_m())
-      mlop::launch_gemv_res(a.data_ptr(), (int)a.stride(0), w.data_ptr(), residual.data_ptr(), (int)M, (int)N,
-                            (int)K, cur_stream());
-    else
-      mlop::launch_ws(a.data_ptr(), (int)a.stride(0), w.data_ptr(), (int)K, residual.data_ptr(), (int)N, (int)M,
-                      (int)N, (int)K, 5, false, mlop::RopeEpi{}, 0.f, cur_stream());
-    return true;
-  }
-  mlop::RopeEpi re{};
-  re.ss_out = ss_out.data_ptr<float>();
-  re.ss_tot = re.ss_out + M * (N / 128);
   c10::DeviceGuard g(a.device());
-  if (mlop::mid_chain_ok((int)M, (int)N, (int)K, 0))  // 5-64 rows: the planner's split-K tiles finish themselves
-    return mlop::launch_mid_res_ss(a.data_ptr(), (int)a.stride(0), w.data_ptr(), residual.data_ptr(),
-                                   (int)residual.stride(0), (int)M, (int)N, (int)K, re.ss_tot, cur_stream());
-  return mlop::launch_w4_chain(4, a.data_ptr(), (int)a.stride(0), w.data_ptr(), residual.data_ptr(),
-                               (int)residual.stride(0), (int)M, (int)N, (int)K, re, cur_stream());
+  return mlop::launch_gemm_chain(mlop::OP_CHAIN_RES_SS, a.data_ptr(), (int)a.stride(0), w.data_ptr(),
+                                 residual.data_ptr(), (int)residual.stride(0), (int)M, (int)N, (int)K,
+                                 mlop::RopeEpi{}, ss_out.data_ptr<float>(), 0.f, cur_stream());
 }
 
 // out = epi(diag(rsqrt(ss / K + eps)) . a . w^T): a is the un-normalised residual, ss_in its
-// partial sums of squares (gemm_res_ss), w the consumer weight with the norm weight folded in
+// sums of squares (gemm_res_ss), w the consumer weight with the norm weight folded in
 bool gemm_rs(Tensor out, Tensor a, Tensor w, Tensor ss_in, double eps, int64_t epi) {
-  TORCH_CHECK(a.is_cuda() && a.scalar_type() == at::kBFloat16 && a.dim() == 2 && a.stride(1) == 1 &&
-                  a.stride(0) % 8 == 0, "a must be bf16 [M, K], 16-B aligned rows");
+  check_a(a);
   check_bf16(w, "w"); check_bf16(out, "out");
   const int64_t M = a.size(0), K = a.size(1), N = w.size(0);
   TORCH_CHECK(w.dim() == 2 && w.size(1) == K, "w [N, K]");
@@ -381,86 +412,28 @@ bool gemm_rs(Tensor out, Tensor a, Tensor w, Tensor ss_in, double eps, int64_t e
                   out.stride(0) % 8 == 0, "out [M, N or N/2]");
   TORCH_CHECK(K % 128 == 0, "K % 128");
   check_ss(ss_in, M, K, "ss");
-  if (M <= mlop::decode_chain_max_m()) {  // decode sizes: PRO_RS, row factors from the streamed chunks (ss_in unused)
-    if (!mlop::decode_chain_takes((int)M, (int)N, (int)K, (int)epi)) return false;
-    c10::DeviceGuard g(a.device());
-    if (M <= mlop::gemv_chain_max_m())
-      mlop::launch_gemv_rs(a.data_ptr(), (int)a.stride(0), w.data_ptr(), out.data_ptr(), (int)out.stride(0), (int)M,
-                           (int)N, (int)K, (int)epi, mlop::RopeEpi{}, (float)eps, cur_stream());
-    else
-      mlop::launch_ws(a.data_ptr(), (int)a.stride(0), w.data_ptr(), (int)K, out.data_ptr(), (int)out.stride(0),
-                      (int)M, (int)N, (int)K, (int)epi, true, mlop::RopeEpi{}, (float)eps, cur_stream());
-    return true;
-  }
-  mlop::RopeEpi re{};
-  re.ss_in = ss_in.data_ptr<float>() + M * (K / 128);
-  re.ss_inv_k = 1.f / (float)K;
-  re.ss_eps = (float)eps;
   c10::DeviceGuard g(a.device());
-  if (mlop::mid_chain_ok((int)M, (int)N, (int)K, (int)epi))  // 5-64 rows: the planner's SiLU tile, row-scaled
-    return mlop::launch_mid_rs(a.data_ptr(), (int)a.stride(0), w.data_ptr(), out.data_ptr(), (int)out.stride(0),
-                               (int)M, (int)N, (int)K, re.ss_in, (float)eps, cur_stream());
-  return mlop::launch_w4_chain((int)epi | 8, a.data_ptr(), (int)a.stride(0), w.data_ptr(), out.data_ptr(),
-                               (int)out.stride(0), (int)M, (int)N, (int)K, re, cur_stream());
+  return mlop::launch_gemm_chain(mlop::OP_CHAIN_RS | (int)epi, a.data_ptr(), (int)a.stride(0), w.data_ptr(),
+                                 out.data_ptr(), (int)out.stride(0), (int)M, (int)N, (int)K, mlop::RopeEpi{},
+                                 ss_in.data_ptr<float>(), (float)eps, cur_stream());
 }
 
 // QKV projection of the norm chain: rows scaled as gemm_rs, then RoPE + paged K / staged V
 bool gemm_rs_rope(Tensor q_out, Tensor k_cache, Tensor v_cache, Tensor a, Tensor w, Tensor pos, Tensor cos_sin,
                   Tensor slots, Tensor ss_in, double eps) {
-  TORCH_CHECK(a.is_cuda() && a.scalar_type() == at::kBFloat16 && a.dim() == 2 && a.stride(1) == 1 &&
-                  a.stride(0) % 8 == 0, "a must be bf16 [M, K], 16-B aligned rows");
-  check_bf16(w, "w"); check_bf16(q_out, "q_out"); check_bf16(k_cache, "k_cache");
-  check_bf16(v_cache, "v_cache"); check_i32(pos, "pos"); check_i32(slots, "slots");
-  TORCH_CHECK(cos_sin.is_cuda() && cos_sin.scalar_type() == at::kFloat && cos_sin.is_contiguous(), "cos_sin f32");
+  const mlop::RopeEpi re = rope_args(q_out, k_cache, v_cache, a, w, pos, cos_sin, slots);
   const int64_t M = a.size(0), K = a.size(1), N = w.size(0);
-  TORCH_CHECK(w.dim() == 2 && w.size(1) == K && K % 64 == 0, "w [N, K], K % 64");
-  TORCH_CHECK(q_out.dim() == 3 && k_cache.dim() == 4 && v_cache.dim() == 4, "ranks");
-  const int64_t Hq = q_out.size(1), D = q_out.size(2), Hkv = k_cache.size(1), BS = k_cache.size(2);
-  TORCH_CHECK(D == 128 && k_cache.size(3) == D && v_cache.sizes() == k_cache.sizes(),
-              "head_dim 128; k and v [NB,Hkv,BS,D]");
-  TORCH_CHECK(N == (Hq + 2 * Hkv) * D && q_out.size(0) == M, "qkv width / q_out rows");
-  TORCH_CHECK(pos.numel() == M && slots.numel() == M, "pos/slots length");
-  TORCH_CHECK(cos_sin.dim() == 2 && cos_sin.size(1) == D, "cos_sin [max_pos, D]");
   TORCH_CHECK(K % 128 == 0, "K % 128");
   check_ss(ss_in, M, K, "ss");
-  mlop::RopeEpi re{(uint16_t*)q_out.data_ptr(), (uint16_t*)k_cache.data_ptr(),
-                   (uint16_t*)v_cache.data_ptr(), pos.data_ptr<int>(), cos_sin.data_ptr<float>(),
-                   slots.data_ptr<int>(), (int)Hq, (int)Hkv, (int)BS};
-  if (M <= mlop::decode_chain_max_m()) {  // decode sizes: PRO_RS + the RoPE / paged K/V epilogue (ss_in unused)
-    if (!mlop::decode_chain_takes((int)M, (int)N, (int)K, 3)) return false;
-    c10::DeviceGuard g(a.device());
-    if (M <= mlop::gemv_chain_max_m())
-      mlop::launch_gemv_rs(a.data_ptr(), (int)a.stride(0), w.data_ptr(), nullptr, 0, (int)M, (int)N, (int)K, 3, re,
-                           (float)eps, cur_stream());
-    else
-      mlop::launch_ws(a.data_ptr(), (int)a.stride(0), w.data_ptr(), (int)K, nullptr, 0, (int)M, (int)N, (int)K, 3,
-                      true, re, (float)eps, cur_stream());
-    return true;
-  }
-  re.ss_in = ss_in.data_ptr<float>() + M * (K / 128);
-  re.ss_inv_k = 1.f / (float)K;
-  re.ss_eps = (float)eps;
-  if (mlop::mid_chain_ok((int)M, (int)N, (int)K, 3)) {  // 5-64 rows
-    c10::DeviceGuard g(a.device());
-    if (mlop::ws_prefer((int)M, (int)N, (int)K, 3)) {  // row scale computed from the streamed rows
-      mlop::launch_ws(a.data_ptr(), (int)a.stride(0), w.data_ptr(), (int)K, nullptr, 0, (int)M, (int)N, (int)K, 3,
-                      true, re, (float)eps, cur_stream());
-      return true;
-    }
-    return mlop::launch_gemm_rope(a.data_ptr(), (int)a.stride(0), w.data_ptr(), (int)M, (int)N, (int)K, re,
-                                  cur_stream());  // the slab path: row scale in the RoPE + cache reduce
-  }
-  if (!mlop::w4_chain_ok((int)M, (int)N, (int)K)) return false;
   c10::DeviceGuard g(a.device());
-  return mlop::launch_w4_chain(3 | 8, a.data_ptr(), (int)a.stride(0), w.data_ptr(), nullptr, 0, (int)M, (int)N,
-                               (int)K, re, cur_stream());
+  return mlop::launch_gemm_chain(mlop::OP_CHAIN_RS_ROPE, a.data_ptr(), (int)a.stride(0), w.data_ptr(), nullptr, 0,
+                                 (int)M, (int)N, (int)K, re, ss_in.data_ptr<float>(), (float)eps, cur_stream());
 }
 
 // out = rmsnorm(residual += a . w^T) * norm_w through the split-K path; false = not taken
 bool gemm_add_rmsnorm(Tensor out, Tensor residual, Tensor a, Tensor w, Tensor norm_w, Tensor ws,
                       double eps) {
-  TORCH_CHECK(a.is_cuda() && a.scalar_type() == at::kBFloat16 && a.dim() == 2 && a.stride(1) == 1 &&
-                  a.stride(0) % 8 == 0, "a must be bf16 [M, K], 16-B aligned rows");
+  check_a(a);
   check_bf16(w, "w"); check_bf16(out, "out"); check_bf16(residual, "residual");
   check_bf16(norm_w, "norm_w");
   const int64_t M = a.size(0), K = a.size(1), N = w.size(0);
@@ -479,8 +452,7 @@ bool gemm_add_rmsnorm(Tensor out, Tensor residual, Tensor a, Tensor w, Tensor no
 // weight-streaming MFMA GEMM (gemm_ws.hip), plain / SiLU-mul / residual-add forms, optionally
 // with the row-scale prologue; false = shape not taken
 bool gemm_ws(Tensor out, Tensor a, Tensor w, int64_t epi, bool rs, double eps) {
-  TORCH_CHECK(a.is_cuda() && a.scalar_type() == at::kBFloat16 && a.dim() == 2 && a.stride(1) == 1 &&
-                  a.stride(0) % 8 == 0, "a must be bf16 [M, K], 16-B aligned rows");
+  check_a(a);
   check_bf16(w, "w"); check_bf16(out, "out");
   const int64_t M = a.size(0), K = a.size(1), N = w.size(0);
   TORCH_CHECK(w.dim() == 2 && w.size(1) == K && w.stride(0) == K, "w [N, K] contiguous");
@@ -488,32 +460,14 @@ bool gemm_ws(Tensor out, Tensor a, Tensor w, int64_t epi, bool rs, double eps) {
   TORCH_CHECK(out.dim() == 2 && out.size(0) == M && out.size(1) == (epi == 1 ? N / 2 : N) && out.stride(1) == 1,
               "out [M, N or N/2]");
   TORCH_CHECK(!(rs && epi == 5), "residual form has no row scale");
-  if (!mlop::ws_takes((int)M, (int)N, (int)K, (int)epi)) return false;
+  if (!mlop::ws_takes(mlop::gemm_live_env(), (int)M, (int)N, (int)K, (int)epi)) return false;
   c10::DeviceGuard g(a.device());
   mlop::launch_ws(a.data_ptr(), (int)a.stride(0), w.data_ptr(), (int)K, out.data_ptr(), (int)out.stride(0), (int)M,
                   (int)N, (int)K, (int)epi, rs, mlop::RopeEpi{}, (float)eps, cur_stream());
   return true;
 }
 
-int64_t gemm_ws_max_m(int64_t set) { return mlop::gemm_ws_max_m((int)set); }
 void gemm_ws_plan(int64_t rb, int64_t u, int64_t nt) { mlop::gemm_ws_plan((int)rb, (int)u, (int)nt); }
-int64_t gemm_ws_small_m(int64_t set) { return mlop::gemm_ws_small_m((int)set); }
-int64_t gemm_ws_rope_m(int64_t set) { return mlop::gemm_ws_rope_m((int)set); }
-int64_t flash_persist(int64_t set) { return mlop::flash_persist((int)set); }
-int64_t flash_stream(int64_t set) { return mlop::flash_stream((int)set); }
-int64_t gemm_grouped_balance(int64_t set) { return mlop::gemm_grouped_balance((int)set); }
-int64_t gemm_grouped_order(int64_t set) { return mlop::gemm_grouped_order((int)set); }
-int64_t moe_mid_tok(int64_t set) { return mlop::moe_mid_tok((int)set); }
-int64_t gemm_mid_chain(int64_t set) { return mlop::gemm_mid_chain((int)set); }
-bool mid_chain_ok(int64_t M, int64_t N, int64_t K, int64_t epi) {
-  return mlop::mid_chain_ok((int)M, (int)N, (int)K, (int)epi);
-}
-
-bool gemv_chain_supported(int64_t M, int64_t N, int64_t K, int64_t epi) {
-  return mlop::decode_chain_takes((int)M, (int)N, (int)K, (int)epi);
-}
-
-int64_t decode_chain_max_m() { return mlop::decode_chain_max_m(); }
 
 // grouped (MoE): rows of a sorted by group, offsets [G+1]; w [G, N, K]
 void grouped_gemm(Tensor out, Tensor a, Tensor w, Tensor offsets, int64_t max_rows, int64_t epi,
@@ -967,32 +921,32 @@ TORCH_LIBRARY(mlop, m) {
   m.def("ep_mem_mode(int h) -> int", &ep_mem_mode);
   m.def("ep_destroy(int h) -> ()", &ep_destroy);
   m.def("gemm_workspace(int M, int N, int K, int epi) -> int", &gemm_workspace);
-  m.def("gemm_big_variant(int set=-1) -> int", &gemm_big_variant);
-  m.def("gemm_half_tile(int set=-1) -> int", &gemm_half_tile);
-  m.def("gemm_small_nt(int set=-1) -> int", &gemm_small_nt);
-  m.def("attn_kv_nt(int set=-1) -> int", &attn_kv_nt);
-  m.def("gemm_slab_nt(int set=-1) -> int", &gemm_slab_nt);
-  m.def("gemm_rope_split(int set=-1) -> int", &gemm_rope_split);
-  m.def("gemm_split_target(int set=-1) -> int", &gemm_split_target);
-  m.def("gemm_grouped_narrow(int set=-1) -> int", &gemm_grouped_narrow);
-  m.def("gemm_ws_max_m(int set=-1) -> int", &gemm_ws_max_m);
+  m.def("gemm_big_variant(int set=-1) -> int", &knob<mlop::gemm_big_variant>);
+  m.def("gemm_half_tile(int set=-1) -> int", &knob<mlop::gemm_half_tile>);
+  m.def("gemm_small_nt(int set=-1) -> int", &knob<mlop::gemm_small_nt>);
+  m.def("attn_kv_nt(int set=-1) -> int", &knob<mlop::attn_kv_nt>);
+  m.def("gemm_slab_nt(int set=-1) -> int", &knob<mlop::gemm_slab_nt>);
+  m.def("gemm_rope_split(int set=-1) -> int", &knob<mlop::gemm_rope_split>);
+  m.def("gemm_split_target(int set=-1) -> int", &knob<mlop::gemm_split_target>);
+  m.def("gemm_grouped_narrow(int set=-1) -> int", &knob<mlop::gemm_grouped_narrow>);
+  m.def("gemm_ws_max_m(int set=-1) -> int", &knob<mlop::gemm_ws_max_m>);
   m.def("decode_chain_max_m() -> int", &decode_chain_max_m);
   m.def("gemm_ws_plan(int rb, int u, int nt) -> ()", &gemm_ws_plan);
-  m.def("gemm_ws_small_m(int set=-1) -> int", &gemm_ws_small_m);
-  m.def("gemm_ws_rope_m(int set=-1) -> int", &gemm_ws_rope_m);
-  m.def("flash_persist(int set=-1) -> int", &flash_persist);
-  m.def("flash_stream(int set=-1) -> int", &flash_stream);
-  m.def("gemm_grouped_balance(int set=-1) -> int", &gemm_grouped_balance);
-  m.def("gemm_grouped_order(int set=-1) -> int", &gemm_grouped_order);
-  m.def("moe_mid_tok(int set=-1) -> int", &moe_mid_tok);
-  m.def("gemm_mid_chain(int set=-1) -> int", &gemm_mid_chain);
+  m.def("gemm_ws_small_m(int set=-1) -> int", &knob<mlop::gemm_ws_small_m>);
+  m.def("gemm_ws_rope_m(int set=-1) -> int", &knob<mlop::gemm_ws_rope_m>);
+  m.def("flash_persist(int set=-1) -> int", &knob<mlop::flash_persist>);
+  m.def("flash_stream(int set=-1) -> int", &knob<mlop::flash_stream>);
+  m.def("gemm_grouped_balance(int set=-1) -> int", &knob<mlop::gemm_grouped_balance>);
+  m.def("gemm_grouped_order(int set=-1) -> int", &knob<mlop::gemm_grouped_order>);
+  m.def("moe_mid_tok(int set=-1) -> int", &knob<mlop::moe_mid_tok>);
+  m.def("gemm_mid_chain(int set=-1) -> int", &knob<mlop::gemm_mid_chain>);
   m.def("mid_chain_ok(int M, int N, int K, int epi) -> bool", &mid_chain_ok);
-  m.def("moe_mid_max_tokens(int set=-1) -> int", &moe_mid_max_tokens);
+  m.def("moe_mid_max_tokens(int set=-1) -> int", &knob<mlop::moe_mid_max_tokens>);
   m.def("gemm_grouped_plan(int bm, int bn, int stages, int splits) -> ()", &gemm_grouped_plan);
   m.def("gemm_dense_plan(int variant, int bm, int bn, int splits, int stages=0) -> ()", &gemm_dense_plan);
-  m.def("gemm_small_stages(int set=-1) -> int", &gemm_small_stages);
-  m.def("gemm_small_tile(int set=-1) -> int", &gemm_small_tile);
-  m.def("gemm_sk_mode(int set=-1) -> int", &gemm_sk_mode);
+  m.def("gemm_small_stages(int set=-1) -> int", &knob<mlop::gemm_small_stages>);
+  m.def("gemm_small_tile(int set=-1) -> int", &knob<mlop::gemm_small_tile>);
+  m.def("gemm_sk_mode(int set=-1) -> int", &knob<mlop::gemm_sk_mode>);
   m.def("gemm_sk_reserve() -> bool", &gemm_sk_reserve);
   m.def("gemm_sk_workgroups(int M, int N, int K) -> int", &gemm_sk_workgroups);
   m.def("vmm_supported(int device) -> bool", &vmm_supported);
@@ -1003,7 +957,11 @@ TORCH_LIBRARY(mlop, m) {
   m.def("vmm_chunks_ready(Tensor flat) -> int", &vmm_chunks_ready);
   m.def("vmm_error(Tensor flat) -> int", &vmm_error);
   m.def("gemm_rope_supported(int M, int N, int K) -> bool", &gemm_rope_supported);
-  m.def("w4_chain_ok(int M, int N, int K) -> bool", &w4_chain_ok_op);
+  m.def("w4_chain_ok(int M, int N, int K) -> bool", &w4_chain_ok);
+  m.def("chain_ok(int M, int N, int K, int epi) -> bool", &chain_ok);
+  m.def("gemm_route(int M, int N, int K, int op, int n_groups=0, int rows_per_group=0) -> int[]", &gemm_route);
+  m.def("gemm_route_env(int M, int N, int K, int op, int cus, bool sk, int n_groups=0, int rows_per_group=0) -> int[]", &gemm_route_env);
+  m.def("gemm_tile_configs() -> int[]", &gemm_tile_configs);
   m.def("gemm_res_ss(Tensor(a!) residual, Tensor a, Tensor w, Tensor(b!) ss_out) -> bool");
   m.def("gemm_rs(Tensor(a!) out, Tensor a, Tensor w, Tensor ss_in, float eps, int epi) -> bool");
   m.def("gemm_rs_rope(Tensor(a!) q_out, Tensor(b!) k_cache, Tensor(c!) v_cache, Tensor a, Tensor w, "

@@ -35,14 +35,15 @@
 // B = W[e] ([E, N, K]); blockIdx.y enumerates (expert, m-tile) pairs on device.
 #include "common.h"
 #include "launch.h"
+#include "gemm_plan.h"
 #include "rope_epi.h"
+
+#include <stdexcept>
 
 namespace mlop {
 
 enum { EPI_NONE = 0, EPI_SILU_MUL = 1, EPI_ROPE = 3 };
-constexpr int kBK = 64;
 constexpr int kStages = 3;
-constexpr int kMaxSplits = 8;  // plan(): split-K factors are at most 8
 
 // 16-B slot of chunk c in image row r is c ^ swz(r).  Two 128-B rows share one
 // 256-B bank row, so (r>>1)&7 (not r&7) makes the 16 rows of a ds_read_b128 lane
@@ -51,7 +52,7 @@ __device__ __forceinline__ int swz(int r) { return (r >> 1) & 7; }
 
 
 
-// Mid-M norm chain (5-64 rows, launch_mid_res_ss): the O / down projection's split-K GEMM
+// Mid-M norm chain (5-64 rows, launch_gemm_chain): the O / down projection's split-K GEMM
 // finishes itself.  Every split stored its fp32 partial write-through (sc1), waited for it,
 // met its workgroup at a barrier, and one lane draws a relaxed agent-scope ticket on the
 // tile's counter; the split that draws the last ticket reads the partials with sc1 loads only
@@ -316,7 +317,7 @@ __global__ void __launch_bounds__(WM * WN * 64) gemm_kernel(
   const int rows_here = min(BM, m_end - m0);
   if (split) {
     // split-K: fp32 partial slab [kz][M][N] (plain stores; reduce kernel in the next launch).
-    // Mid norm chain (re.ss_cnt set, launch_mid_res_ss): write-through (sc1) stores, then the
+    // Mid norm chain (re.ss_cnt set, launch_gemm_chain): write-through (sc1) stores, then the
     // last split of the tile finishes it in this launch (mid_chain_finish).
     float* P = ws + (size_t)bz * M * N;
     const bool fix = !GROUPED && re.ss_cnt != nullptr;
@@ -535,11 +536,6 @@ int gemm_small_nt(int set) {
 // bit 2 the ping-pong kernel's C (Mixtral batch 256 / 1024 and Llama batch 512 +0.3-0.4 %),
 // bit 3 the four-wave RoPE epilogue's q / K / V (with attn_kv_nt 3: headline +0.5 % over 5 pairs)
 static int g_slab_nt = 15;
-static int g_split_target = 512;  // gemm_split_target op: workgroups the split-K of the 16-row tiles aims at
-int gemm_split_target(int set) {
-  if (set >= 1) g_split_target = set;
-  return g_split_target;
-}
 int gemm_slab_nt(int set) {
   if (set >= 0) g_slab_nt = set;
   return g_slab_nt;
@@ -567,79 +563,6 @@ static void run_cfg(const uint16_t* A, int lda, const uint16_t* B, int ldb, uint
   r.ws_nt = g_slab_nt;
   kern<<<blocks, T, lds, st>>>(A, lda, B, ldb, C, ldc, ws, M, N, K, k_chunk, offsets, n_groups, gx,
                                m_tiles, splits, r);
-}
-
-static int g_small_stages = 3;
-int gemm_small_stages(int set) {
-  if (set >= 0) g_small_stages = set;
-  return g_small_stages;
-}
-
-// Row-fitted narrow tiles for M <= 64 (plan()): 0 = the 64 x 64 tile; 32 / 64 = BN with BM the
-// batch rounded up to 16 / 32 / 64; 1 (default) = BM fitted, BN and ring depth per shape (no padding rows streamed through the A ring: the 16-row
-// tile's 4-stage ring is 10 KB instead of 16, so more workgroups stay resident per CU).
-// Default 64: M <= 32 cold projections 6-17 % faster than the 64 x 64 tile (qkv 18.3 -> 15.3 us,
-// o+norm 14.9 -> 12.9, gate_up 47.1 -> 45.6, down+norm 32.9 -> 27.3 at M = 16; BN 32 loses:
-// profiles/r02_midbatch_decode.md, scripts/run131.sh).  Run-time settable for A/B.
-static int g_small_tile = 1;  // 1 = per-shape (plan); 64 x 64 for M 33-64
-// ring depth of the grouped (MoE) 64-row tiles on narrow N (the down projection): 6 measured
-// neutral on Mixtral batch 32 / 64 (1,651 vs 1,655, 3,142 vs 3,134 tok/s, scripts/run141.sh)
-constexpr int g_grouped_small_stages = 3;
-int gemm_small_tile(int set) {
-  if (set >= 0) g_small_tile = set;
-  return g_small_tile;
-}
-
-// grouped-plan override (scripts/bench_moe_decode.py compares MoE decode tilings in one process):
-// BM, BN, ring stages, K splits; -1 = the planner's own choice.  Only tile shapes launch_plan has
-// a grouped config for are accepted.
-static int g_gp[4] = {-1, -1, -1, -1};
-void gemm_grouped_plan(int bm, int bn, int stages, int splits) {
-  if (bm > 0) {
-    static const int ok[][2] = {{16, 32}, {16, 64}, {32, 32}, {32, 64}, {64, 32}, {64, 64},
-                                {128, 64}, {256, 64}, {256, 128}, {256, 256}};
-    bool found = false;
-    for (const auto& t : ok) found = found || (t[0] == bm && t[1] == bn);
-    if (!found) throw std::runtime_error("gemm_grouped_plan: no grouped config for this tile");
-  }
-  g_gp[0] = bm, g_gp[1] = bn, g_gp[2] = stages, g_gp[3] = splits;
-}
-
-// dense-plan override (scripts/bench_mid_m.py sweeps the mid-M projection tilings in one
-// process): variant (0 = gemm_kernel BM x BN, 1 = 256x256 two-stage, 3 = ping-pong, 5 =
-// four-wave, 6 = four-wave half height), BM, BN, K splits (plain gemm_kernel only), LDS ring
-// depth of the small tiles (0 = the default); -1 = the planner's own choice
-static int g_dp[5] = {-1, -1, -1, -1, 0};
-void gemm_dense_plan(int variant, int bm, int bn, int splits, int stages) {
-  if (variant >= 0 && variant != 0 && variant != 1 && variant != 3 && variant != 5 && variant != 6)
-    throw std::runtime_error("gemm_dense_plan: variant must be 0, 1, 3, 5 or 6");
-  if (variant == 0) {
-    static const int ok[][2] = {{16, 32}, {16, 64}, {32, 32}, {32, 64}, {64, 32}, {64, 64}, {128, 64}, {256, 64}, {256, 128}};
-    bool found = false;
-    for (const auto& t : ok) found = found || (t[0] == bm && t[1] == bn);
-    if (!found) throw std::runtime_error("gemm_dense_plan: no dense config for this tile");
-  }
-  g_dp[0] = variant, g_dp[1] = bm, g_dp[2] = bn, g_dp[3] = splits, g_dp[4] = stages > 0 ? stages : 0;
-}
-
-// large-M kernel choice (plan() variants below), settable at run time (gemm_big_variant op) so
-// A/B microbenches run in one process
-static int g_big_variant = 5;
-int gemm_big_variant(int set) {
-  if (set >= 0) g_big_variant = set;
-  return g_big_variant;
-}
-// the grouped <= 32-rows-per-expert rule (plan() below) on / off (gemm_grouped_narrow op)
-static int g_grouped_narrow = 1;
-int gemm_grouped_narrow(int set) {
-  if (set >= 0) g_grouped_narrow = set;
-  return g_grouped_narrow;
-}
-// the planner's half-height four-wave tile (variant 6) on / off (gemm_half_tile op, A/B runs)
-static int g_half_tile = 1;
-int gemm_half_tile(int set) {
-  if (set >= 0) g_half_tile = set;
-  return g_half_tile;
 }
 
 // ---------------------------------------------------------------------------
@@ -680,37 +603,12 @@ struct SkArgs {
   int n_base;   // first stream-K block (grouped: the worst-case tile count of the grid)
   int cus;      // CUs the split was planned for
   int min_half; // shortest K-range (K-tiles) the planner may cut
-  int skip_dead;  // 1: quadrants past the last row issue no MFMAs (MLOP_GEMM_SKIP_DEAD=0: A/B)
+  int skip_dead;  // 1: quadrants past the last row issue no MFMAs (always 1 on the host side: g_skip_dead)
   int balance;    // grouped: an expert over c > 1 m-tiles gets c EQUAL row ranges (gemm_grouped_balance)
   int order;      // grouped: 0 = (expert, m-tile) slot fastest, 1 = expert-major (gemm_grouped_order)
 };
 
-// d for the r = T % cus tail tiles of a T-tile launch: each is cut into d equal K-ranges
-// (d | nk, so no range straddles two tiles), one per extra workgroup, d <= cus / r, when the
-// cost model (in K-tile times, calibrated on scripts/bench_proj.py) beats the tail round's nk:
-//   nk / d                   the range itself
-//   max(2, 0.04 * r * d)     256 KB fp32 partial per workgroup, HBM-bound when all write
-//   2 * (d - 1, or d)        the last contributor's slot reads (one CU, ~3 us per slot)
-//   1                        a second pipeline fill + ticket
-// 0: keep the data-parallel grid.  Host (plain launches) and device (grouped launches, whose
-// tile count depends on the routing) evaluate the same function.
-__host__ __device__ inline int sk_choose_d(int T, int nk, int cus, int min_half) {
-  const int r = T % cus;
-  if (r == 0) return 0;
-  float best = 0.9f * nk;  // require a 10 % gain on the tail round
-  int best_d = 0;
-  const int dmax = cus / r < 32 ? cus / r : 32;
-  for (int d = 2; d <= dmax; ++d) {
-    if (nk % d || nk / d < min_half) continue;
-    const float w = 0.04f * r * d;
-    const float cost = nk / d + (w > 2.f ? w : 2.f) + 2.f * (d >= 3 ? d : d - 1) + 1.f;
-    if (cost < best) {
-      best = cost;
-      best_d = d;
-    }
-  }
-  return best_d;
-}
+// sk_choose_d (gemm_plan.h): d, the K ranges each of the r = T % cus tail tiles is cut into.
 
 // Stream-K workgroup Lb (of n_sk starting at block n0) -> its range index, XCD-contiguous:
 // blocks are dealt to the 8 XCDs round-robin (block & 7), so consecutive ranges -- which walk
@@ -1135,15 +1033,13 @@ __global__ void __launch_bounds__(512, 1) gemm_pp_kernel(
 // Stream-K buffers (per device, allocated once outside graph capture by gemm_sk_reserve):
 // 2 partial slots per stream-K workgroup and kCntRegions rotating sets of tail-tile counters,
 // so back-to-back launches never share a counter set while one may still be resetting.
-constexpr int kSkMaxWg = 256, kCntRegions = 64;
+constexpr int kCntRegions = 64;
 struct SkBuf {
   float* ws = nullptr;
   int* cnt = nullptr;
   int next = 0, cus = 0;
 };
 static SkBuf g_sk[16];
-static int g_sk_mode = 1;
-static const int g_sk_min_iters = 16;
 static const int g_skip_dead = 1;
 // gemm_grouped_balance op: 1 = quadrant-aligned equal row ranges for an expert over several
 // m-tiles (8 x 257 rows gate_up 677 -> 639 us, down 353 -> 308; Mixtral batch 1024 +0.75 %);
@@ -1161,11 +1057,6 @@ int gemm_grouped_order(int set) {
   return g_grouped_order;
 }
 
-int gemm_sk_mode(int set) {
-  if (set >= 0) g_sk_mode = set;
-  return g_sk_mode;
-}
-
 bool gemm_sk_reserve() {
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return false;
@@ -1176,7 +1067,7 @@ bool gemm_sk_reserve() {
   b.cus = std::min(cus, kSkMaxWg);
   float* ws = nullptr;
   int* cnt = nullptr;
-  if (hipMalloc((void**)&ws, (size_t)2 * kSkMaxWg * 256 * 256 * sizeof(float)) != hipSuccess) return false;
+  if (hipMalloc((void**)&ws, (size_t)kSkScratchFloats * sizeof(float)) != hipSuccess) return false;
   if (hipMalloc((void**)&cnt, (size_t)kCntRegions * kSkMaxWg * sizeof(int)) != hipSuccess) {
     (void)hipFree(ws);
     return false;
@@ -1192,24 +1083,27 @@ bool gemm_sk_reserve() {
   return true;
 }
 
-// Split of a plain launch's T tiles: n_dp data-parallel workgroups + a stream-K tail
-// (n_sk = 0: no tail).  The r = T % C tail tiles are each cut into d equal K-ranges (d | nk,
-// so no range straddles two tiles), one per extra workgroup, d <= C / r, when the cost model
-// (in K-tile times, calibrated on scripts/bench_proj.py) beats the tail round's nk:
-//   ipw                      the range itself
-//   max(2, w * 0.04)         256 KB fp32 partial per workgroup, HBM-bound when all write
-//   (d - 1 or d) * 2         the last contributor's slot reads (one CU, ~3 us per slot)
-//   1                        a second pipeline fill + ticket
-// Ranges that straddle tiles (general stream-K) were measured slower than the data-parallel
-// grid whenever the tail exceeds half the chip: twice the partial traffic, two fills.
-static int sk_min_half() { return std::max(1, g_sk_min_iters / 2); }
-
+// the current device's scratch, or null when it is not reserved or gemm_sk_mode is 0
 static SkBuf* sk_buf() {
   int dev = 0;
-  if (!g_sk_mode || hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return nullptr;
+  if (!gemm_knobs().sk_mode || hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return nullptr;
   SkBuf& b = g_sk[dev];
   return b.ws && b.cus > 0 ? &b : nullptr;
 }
+
+// the planner's environment here and now: the knobs and the current device's two facts
+PlanEnv gemm_live_env() {
+  PlanEnv e = gemm_knobs();
+  int dev = 0;
+  if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 16) {
+    e.sk = g_sk[dev].ws != nullptr;
+    e.cus = g_sk[dev].cus;
+  }
+  return e;
+}
+
+// a rotated ticket-counter region (kSkMaxWg counters, zero between launches)
+static int* sk_tickets(SkBuf* b) { return b->cnt + (size_t)(b->next++ % kCntRegions) * kSkMaxWg; }
 
 // partial-tile scratch for the four-wave kernel's split tail (gemm_w4.hip): the same per-device
 // slot buffer and a rotated ticket-counter region; false when the buffers are not reserved
@@ -1217,7 +1111,7 @@ bool gemm_sk_scratch(float** ws, int** cnt, int* cus) {
   SkBuf* b = sk_buf();
   if (!b) return false;
   *ws = b->ws;
-  *cnt = b->cnt + (size_t)(b->next++ % kCntRegions) * kSkMaxWg;
+  *cnt = sk_tickets(b);
   *cus = b->cus;
   return true;
 }
@@ -1228,29 +1122,30 @@ bool gemm_sk_available(int* cus) {
   return b != nullptr;
 }
 
-static SkArgs sk_plan(int T, int nk, int& n_sk) {
+// Split of a plain launch's T tiles: n_dp data-parallel workgroups + a stream-K tail of the
+// route's sk_wgs workgroups (0: no tail).  The r = T % C tail tiles are each cut into the
+// route's sk_d equal K-ranges (sk_choose_d, gemm_plan.h), one per extra workgroup.
+// Ranges that straddle tiles (general stream-K) were measured slower than the data-parallel
+// grid whenever the tail exceeds half the chip: twice the partial traffic, two fills.
+static SkArgs sk_args(const Route& rt, int T, int nk) {
   SkArgs a{T, T, 1, 0, nullptr, nullptr, T, 256, sk_min_half(), g_skip_dead};
-  n_sk = 0;
   SkBuf* b = sk_buf();
-  if (!b) return a;
-  const int d = sk_choose_d(T, nk, b->cus, sk_min_half());
-  if (!d) return a;
+  if (!rt.sk_d || !b) return a;
   const int r = T % b->cus;
   a.n_dp = T - r;
   a.t0 = T - r;
-  a.ipw = nk / d;
+  a.ipw = nk / rt.sk_d;
   a.n_iters = r * nk;
   a.ws = b->ws;
-  a.cnt = b->cnt + (size_t)(b->next++ % kCntRegions) * kSkMaxWg;
+  a.cnt = sk_tickets(b);
   a.n_base = a.n_dp;
   a.cus = b->cus;
-  n_sk = r * d;
   return a;
 }
 
 template <int EPI, bool GROUPED = false>
-static void run_pp(const uint16_t* A, int lda, const uint16_t* B, int ldb, uint16_t* C, int ldc, int M,
-                   int N, int K, hipStream_t st, const RopeEpi& re, const int* offsets = nullptr,
+static void run_pp(const Route& rt, const uint16_t* A, int lda, const uint16_t* B, int ldb, uint16_t* C, int ldc,
+                   int M, int N, int K, hipStream_t st, const RopeEpi& re, const int* offsets = nullptr,
                    int n_groups = 0) {
   constexpr size_t ring = 2ull * (256 + 256) * kBK * 2;
   constexpr size_t epi = EPI == EPI_ROPE ? 256ull * (256 + 8) * 2
@@ -1266,8 +1161,8 @@ static void run_pp(const uint16_t* A, int lda, const uint16_t* B, int ldb, uint1
   const int gx = (N + 255) / 256, gy = (M + 255) / 256 + (GROUPED ? n_groups : 0);
   constexpr int group_m = 4;
   const int gm = std::max(1, std::min(group_m, gy));
-  int n_sk = 0;
-  SkArgs sk = sk_plan(gx * gy, K / kBK, n_sk);
+  SkArgs sk = sk_args(rt, gx * gy, K / kBK);
+  int n_sk = sk.ws ? rt.sk_wgs : 0;
   // expert weights non-temporal where the expert fits one 256-row m-tile (decided per tile on
   // device): Mixtral batch 256 (64 rows per expert on average) +3.9 %; nt on every expert lost
   // 1.5 % at batch 1024, where the spill m-tiles of the > 256-row experts re-read the weights
@@ -1283,7 +1178,7 @@ static void run_pp(const uint16_t* A, int lda, const uint16_t* B, int ldb, uint1
     sk = SkArgs{T_max, T_max, 1, 0, nullptr, nullptr, T_max, 256, sk_min_half(), g_skip_dead, g_grouped_balance, g_grouped_order};
     if (b) {
       sk.ws = b->ws;
-      sk.cnt = b->cnt + (size_t)(b->next++ % kCntRegions) * kSkMaxWg;
+      sk.cnt = sk_tickets(b);
       sk.cus = b->cus;
       n_sk = b->cus;
     }
@@ -1301,445 +1196,142 @@ static void run_pp(const uint16_t* A, int lda, const uint16_t* B, int ldb, uint1
   kern<<<gx * gy, 512, lds, st>>>(A, lda, B, ldb, C, ldc, M, N, K, gx, gy, gm, r, offsets, n_groups, sk);
 }
 
-struct Plan {
-  int BM, BN, splits, k_chunk, m_tiles, variant;
-  int stages;  // LDS-DMA ring depth of the small-M tiles (0: g_small_stages)
-  bool nosplit;  // grouped: one K range (the mid-size MoE split-K below is skipped)
-};
-
-
-// Tile choice by the (per-group) row count:
-//   M <= 64 / 128: narrow tiles, many WGs (weight streaming);  M <= 256: the whole
-//   batch in one tile (weights read once), BN by how many N tiles fill the chip;
-//   large M: variant 0 = 256x128 (3-stage ring), 1 = 256x256 (2-stage, 128x64 per
-//   wave: half the LDS + L2 bytes per FLOP), 2 = 256x256 + setprio around MFMAs,
-//   3 = 256x256 two-group ping-pong (gemm_pp_kernel), 5 (default) = the four-wave kernel with
-//   the hand-scheduled asm K-loop (gemm_w4.hip) where its grid fills the chip, else 3.  (A four-wave 128x128-per-wave
-//   variant was measured 10-20% slower: profiles/r02_gemm_fourwave_rejected.md.)
-// true when the stream-K tail is available here and splits ALL T (<= C / 2) tiles
-static bool sk_halves_ok(long T, int nk) {
-  const SkBuf* b = sk_buf();
-  return b && T * 2 <= b->cus && sk_choose_d((int)T, nk, b->cus, sk_min_half()) >= 2;
-}
-
-static Plan plan(int M, int N, int K, bool grouped, int n_groups, int rows_per_group) {
-  Plan p{};
-  p.variant = 0;
-  const int mrows = grouped ? rows_per_group : M;
-  // grouped (MoE): the ping-pong kernel from ~56 routed rows per expert.  Its 256 x 256 tile
-  // streams each expert's weight panel once per n-tile and skips the MFMAs of empty 64-row
-  // quadrants, so a half-empty expert tile costs less than the extra m-tiles (each a second walk
-  // of the expert's weights) of the narrower kernels: Mixtral gate_up / down at 512 routed rows
-  // 474 -> 370 / 266 -> 200 us, 1024 rows 692 -> 389 / 375 -> 208 us; 48 rows per expert equal
-  // (scripts/bench_moe_decode.py, profiles/r05_moe_decode.md)
-  constexpr int pp_group_min_rows = 56;
-  if (grouped && mrows >= pp_group_min_rows && K % kBK == 0 && N % 256 == 0) {
-    p.BM = 256; p.BN = 256; p.variant = 3;  // grouped ping-pong
-  } else if (mrows <= 64 && !grouped && g_small_tile == 1) {
-    // per shape (scripts/run137.sh, cold us at M = 16): wide N (gate_up) 64 columns with a
-    // 6-deep ring (47.0 -> 44.8); narrow N 32 columns with an 8-deep ring at BM 16 (qkv
-    // 15.3 -> 13.5, o / down unchanged): more weight bytes in flight per CU
-    p.BM = mrows <= 16 ? 16 : mrows <= 32 ? 32 : 64;
-    p.BN = 64;
-    // (M 17-32 narrow projections on the 32-column 8-deep tiles of M <= 16: 1-2 % slower end to
-    // end at batch 24 / 32, scripts/history INDEX run140)
-    if (p.BM == 16) {
-      const bool wide = N >= 16384;
-      p.BN = wide ? 64 : 32;
-      p.stages = wide ? (p.BM == 16 ? 6 : 0) : 8;
-    } else if (p.BM == 64) {
-      // M 33-64: narrow N on the 6-deep ring (run133: qkv 19.8 -> 18.4, down+norm 35.9 -> 32.0 us),
-      // gate_up on a 4-deep one (run145: 48.2 -> 47.1 at M = 64, 6 stages lose: 50.4)
-      p.stages = N < 16384 ? 6 : 4;
-    }
-  } else if (mrows <= 64 && !grouped && (g_small_tile == 32 || g_small_tile == 64)) {
-    p.BM = mrows <= 16 ? 16 : mrows <= 32 ? 32 : 64;
-    p.BN = g_small_tile;
-  } else if (mrows <= 64) {
-    p.BM = 64;
-    p.BN = 64;
-    // grouped (MoE at a few dozen rows per expert), narrow down projection: ring depth knob
-    if (grouped && N < 16384) p.stages = g_grouped_small_stages;
-    // grouped at <= 32 rows per expert (Mixtral batch 16-64): down on 32 x 64 tiles with a
-    // 6-deep ring and ONE K range, gate_up on a 4-deep ring (scripts/bench_moe_decode.py, cold
-    // expert weights, profiles/r05_moe_decode.md: down at 128 routed rows 172.4 -> 160.4 us,
-    // 5.45 -> 5.86 TB/s; gate_up 318.2 -> 315.9)
-    if (grouped && g_grouped_narrow && mrows <= 32) {
-      if (N < 16384) { p.BM = 32; p.stages = 6; p.nosplit = true; }
-      else p.stages = 4;
-    }
-  }
-  else if (mrows <= 128) { p.BM = 128; p.BN = 64; }
-  else if (mrows <= 256) {
-    constexpr int bn_min_tiles = 192;
-    p.BM = 256;
-    p.BN = ((N + 127) / 128 >= bn_min_tiles) ? 128 : 64;
-  } else {
-    const int big = g_big_variant;
-    constexpr int big_min_m = 1024;
-    p.BM = 256;
-    p.BN = 128;
-    // 128: o / down at 2049-2816 rows (the mixed steps of batch ~512: 144-176 tiles, no K-half
-    // tail for the four-wave kernel) ran on the 256 x 128 kernel at 0.55x hipBLASLt; the
-    // ping-pong kernel's stream-K tail takes them (o at M = 2560: 122 -> 88 us, down 394 -> 269;
-    // scripts/history/r4_m2560.sh)
-    constexpr int pp_min_tiles = 128;
-    const long t256 = (long)((M + 255) / 256) * ((N + 255) / 256);
-    // below pp_min_tiles the 256x256 grid leaves CUs idle, unless the stream-K tail can cut
-    // every tile in two (T <= C / 2): o / down at M = 2040 (128 tiles)
-    const bool pp_ok = K % kBK == 0 && (t256 >= pp_min_tiles || sk_halves_ok(t256, K / kBK));
-    // variant 5: the four-wave kernel where its grid fills the chip: >= w4_min_tiles tiles, or
-    // a tail it can cut in K-halves (o / down at M = 2048: 128 tiles -> 256 half-tiles); else
-    // the ping-pong kernel with its general stream-K tail
-    constexpr int w4_min_tiles = 192;
-    const bool w4_fills = t256 >= w4_min_tiles || gemm_w4_split_ok((int)t256, K / kBK);
-    // Wide projections take the large-M kernels from 512 rows: gate_up / lm_head at M = 512 /
-    // 768 ran 127 -> 87 / 191 -> 153 us (8B) and 511 -> 404 us (70B gate_up), batch-512 serving
-    // +5.3 %; narrow ones lose there (o / down at M = 512: 31 -> 48 / 66 -> 124 us) and keep the
-    // 256 x 128 kernel (scripts/history/r4_bigminm.sh, r4_bigminm2.sh, r4_widemin.sh).
-    // Below ~72 tiles of 256 x 256 (o / down at M = 512 - 1024: 32 - 64 tiles) the 256 x 128
-    // kernel beats them at every M measured short of 2048 (o at M = 1024: 44.7 vs 48.6 us, down
-    // 114.7 vs 129.5); from 72 tiles (qkv at M = 768, 70B qkv at 512) the large-M kernels win.
-    constexpr int wide_min_m = 512;
-    constexpr int mid_tiles = 72;
-    const int big_from = t256 >= mid_tiles ? std::min(big_min_m, wide_min_m) : std::max(big_min_m, 2048);
-    if (big == 5 && !(mrows >= big_from && !grouped && w4_fills && gemm_w4_ok(M, N, K, K, K))) {
-      if (mrows >= big_from && !grouped && pp_ok) { p.BN = 256; p.variant = 3; }
-    } else if (big && mrows >= big_from && !grouped && (big < 3 || pp_ok)) {
-      p.BN = 256;
-      p.variant = big;
-    }
-    if (!grouped && big == 5) {
-      // long-K narrow projections (down, K = 14336) at 40-71 tiles of 256 x 256 (M 640-1279):
-      // the ping-pong kernel's stream-K tail spreads the few tiles' K over every CU (down at
-      // M = 768: 105 -> 90 us, 1024: 118 -> 108; hipBLASLt 90 / 111)
-      if (p.variant == 0 && K >= 8192 && t256 >= 40 && t256 < mid_tiles && K % kBK == 0 &&
-          sk_halves_ok(t256, K / kBK)) {
-        p.BN = 256;
-        p.variant = 3;
-      }
-      // four-wave vs ping-pong past one full round: the four-wave kernel runs whole rounds of
-      // 256 x 256 tiles (a tail of r <= CUs / 2 tiles in K-halves), the ping-pong kernel ~7 %
-      // slower per tile but with a stream-K tail that balances ANY remainder.  Estimated time in
-      // four-wave tile rounds: w4 = q + (r ? (2r <= C ? 0.55 : 1) : 0), pp = 1.08 T / C + 0.05.
-      // (M = 4608: o 147 -> 134 us, down 476 -> 403, qkv 181 -> 172; the headline's M ~ 4088 is
-      // whole rounds for every projection and stays on the four-wave kernel; bench_mid_m.py)
-      const SkBuf* b = sk_buf();
-      if (p.variant == 5 && b && t256 > b->cus && pp_ok) {
-        const long C = b->cus, q = t256 / C, r = t256 % C;
-        const float w4_est = (float)q + (r == 0 ? 0.f : (2 * r <= C ? 0.55f : 1.f));
-        const float pp_est = 1.08f * (float)t256 / (float)C + 0.05f;
-        if (pp_est < w4_est - 0.03f) p.variant = 3;
-      }
-      // variant 6, the half-height (128 x 256) four-wave tile, where its grid is at most one
-      // round: up to twice the workgroups of the 256 x 256 grid (a lone tile of either height
-      // runs ~1.8x faster than one in a full round, so idle CUs cost more than the half tile's
-      // lower MFMA density).  bench_mid_m.py (profiles/r05_gemm_w4h.md), planner before -> after:
-      // o at M = 1024 / 1536 / 2048 46.2 -> 38.3 / 56.0 -> 47.6 / 65.6 -> 55.2 us, qkv at 384 /
-      // 512 / 1024 43.1 -> 33.1 / 44.4 -> 35.3 / 56.0 -> 47.5; past one round it loses to the
-      // full tile (qkv 1408: 75.9 vs 72.3).  Long K (down): only with its own K-half tail
-      // (t128 <= CUs / 2: 96 -> 256 items, M = 1024 110.8 -> 98.5); without it the full tile's
-      // K-halves win (M = 1152: 153.7 vs 131.1), and below ~80 tiles the 256 x 128 split-K kernel
-      // (M = 512: 83.1 vs 67.6).
-      const long t128 = (long)((M + 127) / 128) * ((N + 255) / 256);
-      const bool long_k = K >= 8192;
-      if (g_half_tile && b && mrows >= 384 && (long_k ? t128 >= 80 && 2 * t128 <= b->cus : t128 >= 64 && t128 <= b->cus) &&
-          (p.variant == 0 || p.variant == 3 || p.variant == 5) && gemm_w4_ok(M, N, K, K, K)) {
-        p.BM = 128;
-        p.BN = 256;
-        p.variant = 6;
-      }
-    }
-  }
-  if (!grouped && g_dp[0] >= 0) {  // bench override (gemm_dense_plan)
-    p.variant = g_dp[0];
-    p.BM = p.variant == 0 ? g_dp[1] : p.variant == 6 ? 128 : 256;
-    p.BN = p.variant == 0 ? g_dp[2] : 256;
-    p.stages = g_dp[4];
-  }
-  if (grouped && g_gp[0] > 0) {  // bench override (gemm_grouped_plan)
-    p.BM = g_gp[0];
-    p.BN = g_gp[1];
-    p.variant = (p.BM == 256 && p.BN == 256) ? 3 : 0;
-    p.stages = g_gp[2] > 0 ? g_gp[2] : 0;
-  }
-  const int n_tiles = (N + p.BN - 1) / p.BN;
-  const int real_m_tiles = (M + p.BM - 1) / p.BM;
-  p.m_tiles = grouped ? real_m_tiles + n_groups : real_m_tiles;
-  p.splits = 1;
-  p.k_chunk = K;
-  const long tiles = (long)n_tiles * real_m_tiles;
-  // run49: down -5..-15% at M 8-64.  The 16-row tiles (M 9-16) aim at 512 workgroups: batch 16
-  // +5.6 / +6.0 % interleaved (scripts/r5_splittarget.sh, r5_splittarget2.sh), while 512 lost
-  // 1.4-1.6 % at batch 24 / 32 (32-row tiles), 5 % at batch 64 and 4 % at 256
-  const int split_target = p.BM <= 16 ? g_split_target : 256;
-  constexpr int split_max_tiles = 160;
-  if (!grouped && tiles < split_max_tiles && K >= 1024 && p.variant != 3 && p.variant < 5) {
-    int s = (int)std::min<long>(8, std::max<long>(1, split_target / tiles));
-    int kc = ((K / s + kBK - 1) / kBK) * kBK;
-    p.splits = (K + kc - 1) / kc;
-    p.k_chunk = kc;
-  }
-  if (!grouped && g_dp[0] == 0 && g_dp[3] >= 1) {
-    const int kc = ((K / g_dp[3] + kBK - 1) / kBK) * kBK;
-    p.splits = (K + kc - 1) / kc;
-    p.k_chunk = kc;
-  }
-  return p;
-}
-
+// Executes a route of the tile, ping-pong or four-wave family (gemm_plan.h): an exact-match
+// lookup of the route's tile configuration in MLOP_GEMM_TILES; a route that names anything
+// else is an error, never another kernel.
 template <int EPI, bool GROUPED>
-static void launch_plan(const Plan& p, const uint16_t* A, int lda, const uint16_t* B, int ldb,
-                        uint16_t* C, int ldc, float* ws, int M, int N, int K, const int* offsets,
-                        int n_groups, hipStream_t st, const RopeEpi& re = RopeEpi{}) {
-#define MLOP_GEMM(bm, bn, wm, wn, stages, prio)                                                   \
-  run_cfg<bm, bn, wm, wn, EPI, GROUPED, stages, prio>(A, lda, B, ldb, C, ldc, ws, M, N, K,        \
-                                                      p.splits, p.k_chunk, offsets, n_groups,     \
-                                                      p.m_tiles, st, re)
-  if constexpr (EPI == EPI_ROPE) {  // whole heads per staged chunk, no split-K (launch_gemm_rope)
-    if (p.BN == 128) MLOP_GEMM(256, 128, 4, 2, 3, false);
-    else if (!GROUPED && p.variant >= 5 && gemm_w4_ok(M, N, K, lda, ldb, ldc))
-      run_w4(EPI, A, lda, B, ldb, C, ldc, M, N, K, st, re, p.BM);
-    else if (!GROUPED && (p.variant == 3 || p.variant >= 5)) run_pp<EPI>(A, lda, B, ldb, C, ldc, M, N, K, st, re);
-    else if (!GROUPED && p.variant == 2) MLOP_GEMM(256, 256, 2, 4, 2, true);
-    else if (!GROUPED) MLOP_GEMM(256, 256, 2, 4, 2, false);
-  } else {
-    // weight-streaming tiles (M <= 128): a deeper LDS-DMA ring keeps more weight bytes in
-    // flight per CU (3 stages x 16 KB per workgroup streamed gate_up at 4.7 TB/s at M = 64)
-    const int sst = p.stages ? p.stages : g_small_stages;
-    if (!GROUPED && p.variant == 6 && p.splits == 1 && gemm_w4_ok(M, N, K, lda, ldb, ldc))
-      run_w4(EPI, A, lda, B, ldb, C, ldc, M, N, K, st, re, 128);
-    else if (!GROUPED && p.variant == 6) run_pp<EPI>(A, lda, B, ldb, C, ldc, M, N, K, st, re);
-    else if (p.BM == 16 && p.BN == 32 && sst >= 8) MLOP_GEMM(16, 32, 1, 2, 8, false);
-    else if (p.BM == 16 && p.BN == 32 && sst >= 6) MLOP_GEMM(16, 32, 1, 2, 6, false);
-    else if (p.BM == 16 && p.BN == 32) MLOP_GEMM(16, 32, 1, 2, 4, false);
-    else if (p.BM == 16 && p.BN == 64 && sst >= 8) MLOP_GEMM(16, 64, 1, 2, 8, false);
-    else if (p.BM == 16 && p.BN == 64 && sst >= 6) MLOP_GEMM(16, 64, 1, 2, 6, false);
-    else if (p.BM == 16 && p.BN == 64) MLOP_GEMM(16, 64, 1, 2, 4, false);
-    else if (p.BM == 32 && p.BN == 32 && sst >= 8) MLOP_GEMM(32, 32, 1, 2, 8, false);
-    else if (p.BM == 32 && p.BN == 32) MLOP_GEMM(32, 32, 1, 2, 4, false);
-    else if (p.BM == 32 && p.BN == 64 && sst >= 6) MLOP_GEMM(32, 64, 1, 4, 6, false);
-    else if (p.BM == 32 && p.BN == 64) MLOP_GEMM(32, 64, 1, 4, 4, false);
-    else if (p.BM == 64 && p.BN == 32) MLOP_GEMM(64, 32, 1, 2, 4, false);
-    else if (p.BM == 64 && p.BN == 64 && sst >= 6) MLOP_GEMM(64, 64, 1, 4, 6, false);
-    else if (p.BM == 64 && p.BN == 64 && sst == 4) MLOP_GEMM(64, 64, 1, 4, 4, false);
-    else if (p.BM == 64) MLOP_GEMM(64, 64, 1, 4, 3, false);
-    else if (p.BM == 128 && g_small_stages >= 5) MLOP_GEMM(128, 64, 2, 2, 5, false);
-    else if (p.BM == 128) MLOP_GEMM(128, 64, 2, 2, 3, false);
-    else if (p.BN == 64) MLOP_GEMM(256, 64, 4, 2, 3, false);
-    else if (p.BN == 128) MLOP_GEMM(256, 128, 4, 2, 3, false);
-    else if (GROUPED && p.variant == 3)
-      run_pp<EPI, true>(A, lda, B, ldb, C, ldc, M, N, K, st, re, offsets, n_groups);
-    else if (!GROUPED && p.variant == 5 && p.splits == 1 && gemm_w4_ok(M, N, K, lda, ldb, ldc))
-      run_w4(EPI, A, lda, B, ldb, C, ldc, M, N, K, st, re);
-    else if (!GROUPED && (p.variant == 3 || p.variant == 5) && p.splits == 1)
-      run_pp<EPI>(A, lda, B, ldb, C, ldc, M, N, K, st, re);
-    else if (!GROUPED && p.variant == 2) MLOP_GEMM(256, 256, 2, 4, 2, true);
-    else if (!GROUPED) MLOP_GEMM(256, 256, 2, 4, 2, false);
+static void launch_route(const Route& rt, const uint16_t* A, int lda, const uint16_t* B, int ldb, uint16_t* C,
+                         int ldc, float* ws, int M, int N, int K, const int* offsets, int n_groups,
+                         hipStream_t st, const RopeEpi& re = RopeEpi{}) {
+  if (rt.family == FAM_PP) return run_pp<EPI, GROUPED>(rt, A, lda, B, ldb, C, ldc, M, N, K, st, re, offsets, n_groups);
+  if ((rt.family == FAM_W4 || rt.family == FAM_W4H) && !GROUPED) {
+    if (!run_w4(EPI, A, lda, B, ldb, C, ldc, M, N, K, st, re, rt.BM)) throw std::runtime_error("gemm: four-wave launch refused");
+    return;
   }
+#define MLOP_GEMM(bm_, bn_, wm_, wn_, st_, prio_, rope_)                                                  \
+  if constexpr (EPI != EPI_ROPE || rope_) {                                                               \
+    if (rt.family == FAM_TILE && rt.BM == bm_ && rt.BN == bn_ && rt.WM == wm_ && rt.WN == wn_ &&          \
+        rt.stages == st_ && rt.setprio == (int)prio_)                                                     \
+      return run_cfg<bm_, bn_, wm_, wn_, EPI, GROUPED, st_, prio_>(A, lda, B, ldb, C, ldc, ws, M, N, K,   \
+                                                                   rt.splits, rt.k_chunk, offsets,        \
+                                                                   n_groups, rt.m_tiles, st, re);         \
+  }
+  MLOP_GEMM_TILES(MLOP_GEMM)
 #undef MLOP_GEMM
+  throw std::runtime_error("gemm: the route names no kernel built for this epilogue");
 }
 
-// stream-K workgroups a plain launch of this shape would add (0: data-parallel grid only)
-int gemm_sk_workgroups(int M, int N, int K) {
-  if (M <= 0 || gemv_takes(M, N, K, EPI_NONE)) return 0;
-  const Plan p = plan(M, N, K, false, 0, 0);
-  if (p.variant != 3 || p.BN != 256 || p.splits != 1) return 0;
-  int n_sk = 0;
-  sk_plan(((M + 255) / 256) * ((N + 255) / 256), K / kBK, n_sk);
-  return n_sk;
+static GemmCall gemm_call(int op, int M, int N, int K, int lda, int ldb, int ldc) {
+  GemmCall c;
+  c.op = op, c.M = M, c.N = N, c.K = K, c.lda = lda, c.ldb = ldb, c.ldc = ldc;
+  return c;
 }
 
-// EPI_ROPE: the plain (no split-K) plan must stage whole heads: BN >= 128, i.e. M > 256.
-// Small M whose plan splits K: the slabs go to the stream-K scratch and the split-K reduce is
-// fused into the RoPE + cache kernel (one launch instead of reduce + rope_cache).
-static bool rope_slabs_ok(const Plan& p, int M, int N) {
-  const SkBuf* b = sk_buf();
-  return p.splits > 1 && p.variant != 3 && p.variant < 5 && b != nullptr &&
-         (size_t)p.splits * M * N <= (size_t)2 * kSkMaxWg * 256 * 256;
+static void launch_splitk_reduce(int epi, uint16_t* C, int ldc, const float* ws, int M, int N, int splits,
+                                 hipStream_t st) {
+  const int outw = epi == EPI_NONE ? N : N / 2;
+  const long total = (long)M * (outw / 8);
+  const int g = (int)std::min<long>((total + 255) / 256, 4096);
+  if (epi == EPI_NONE) splitk_reduce_kernel<EPI_NONE><<<g, 256, 0, st>>>(C, ldc, ws, M, N, splits);
+  else splitk_reduce_kernel<EPI_SILU_MUL><<<g, 256, 0, st>>>(C, ldc, ws, M, N, splits);
 }
 
-// Small-M QKV: K split even where the plain plan keeps one K range (M <= 16: 192 tiles of 16 x
-// 32): the slabs' reduce rides in the RoPE + cache kernel that runs anyway, so a second K range
-// costs one fp32 slab and doubles the workgroups streaming the weights (gemm_rope_split op:
-// the K ranges, 1 = the plain plan).  Interleaved, scripts/r5_ropesplitk.sh: batch 16 +1.9 %,
-// batch 12 +3.0 % (4 ranges: +2.2 / +2.6 %)
-static int g_rope_split_k = 2;
-int gemm_rope_split(int set) {
-  if (set >= 1) g_rope_split_k = set;
-  return g_rope_split_k;
-}
-
-static Plan rope_plan(int M, int N, int K) {
-  Plan p = plan(M, N, K, false, 0, 0);
-  if (g_rope_split_k > 1 && p.splits == 1 && p.variant == 0 && p.BM <= 64 && K >= 2048) {
-    const int kc = ((K / g_rope_split_k + kBK - 1) / kBK) * kBK;
-    p.splits = (K + kc - 1) / kc;
-    p.k_chunk = kc;
+// QKV + RoPE + cache stores on route rt (not refused)
+static void run_rope_route(const Route& rt, const void* A, int lda, const void* B, int M, int N, int K,
+                           const RopeEpi& re, hipStream_t st) {
+  if (rt.family == FAM_GEMV) return launch_gemv_rope(A, lda, B, M, N, K, re, st);
+  if (rt.family == FAM_WS) return launch_ws(A, lda, B, K, nullptr, 0, M, N, K, EPI_ROPE, false, re, 0.f, st);
+  if (rt.finish == FIN_ROPE_SLABS) {  // small M: split-K slabs + fused reduce / RoPE / cache
+    float* ws = sk_buf()->ws;
+    launch_route<EPI_NONE, false>(rt, (const uint16_t*)A, lda, (const uint16_t*)B, K, nullptr, N, ws, M, N, K,
+                                  nullptr, 0, st);
+    return launch_rope_cache_slabs(re, ws, rt.splits, M, N, st);
   }
-  return p;
-}
-
-bool gemm_rope_supported(int M, int N, int K) {
-  if (M <= 0 || N % 128 || K % kBK) return false;
-  if (gemv_takes(M, N, K, EPI_ROPE)) return true;  // decode M <= 8: gemv.hip
-  const Plan p = rope_plan(M, N, K);
-  return ((p.BM == 256 || p.variant == 6) && p.BN >= 128) || rope_slabs_ok(p, M, N);
+  launch_route<EPI_ROPE, false>(rt, (const uint16_t*)A, lda, (const uint16_t*)B, K, nullptr, 0, nullptr, M, N, K,
+                                nullptr, 0, st, re);
 }
 
 bool launch_gemm_rope(const void* A, int lda, const void* B, int M, int N, int K, const RopeEpi& re,
                       hipStream_t st) {
   if (M == 0) return true;
-  if (!gemm_rope_supported(M, N, K)) return false;
-  if (gemv_takes(M, N, K, EPI_ROPE) && lda % 8 == 0) {
-    launch_gemv_rope(A, lda, B, M, N, K, re, st);
-    return true;
-  }
-  if (ws_prefer(M, N, K, EPI_ROPE) && lda % 8 == 0) {  // 5-16 rows: the weight-streaming MFMA kernel
-    launch_ws(A, lda, B, K, nullptr, 0, M, N, K, EPI_ROPE, false, re, 0.f, st);
-    return true;
-  }
-  Plan p = rope_plan(M, N, K);
-  if (!((p.BM == 256 || p.variant == 6) && p.BN >= 128)) {  // small M: split-K slabs + fused reduce / RoPE / cache
-    float* ws = sk_buf()->ws;
-    launch_plan<EPI_NONE, false>(p, (const uint16_t*)A, lda, (const uint16_t*)B, K, nullptr, N, ws,
-                                 M, N, K, nullptr, 0, st);
-    launch_rope_cache_slabs(re, ws, p.splits, M, N, st);
-    return true;
-  }
-  p.splits = 1;
-  p.k_chunk = K;
-  launch_plan<EPI_ROPE, false>(p, (const uint16_t*)A, lda, (const uint16_t*)B, K, nullptr, 0, nullptr,
-                               M, N, K, nullptr, 0, st, re);
+  const Route rt = gemm_route(gemm_live_env(), gemm_call(OP_ROPE, M, N, K, lda, K, 0));
+  if (!rt.ok()) return false;
+  run_rope_route(rt, A, lda, B, M, N, K, re, st);
   return true;
 }
 
-// The large-M decoder's norm chain: O / down add into the residual and leave per-row sums of
-// squares (W4_ADD_SS), gate_up / QKV scale their rows by the RMSNorm factor (W4_RS), so the
-// add + RMSNorm passes over [M, H] disappear (norm weights folded into the consumer weights).
-// Everything launch_w4_chain needs, so the caller decides the chain ONCE per forward (before the
-// first in-place residual update) and never meets a refusal mid-layer: the shape on the
-// four-wave kernel, the stream-K scratch that holds the band tickets reserved, and one ticket
-// per band of BM rows.
-bool w4_chain_ok(int M, int N, int K) {
-  if (M <= 0 || gemv_takes(M, N, K, EPI_NONE) || gemv_takes(M, N, K, EPI_ROPE)) return false;
-  int cus = 0;
-  if (!gemm_sk_available(&cus) || cus <= 0) return false;
-  const Plan p = plan(M, N, K, false, 0, 0);
-  return (p.variant == 5 || p.variant == 6) && p.splits == 1 && p.BN == 256 && (M + p.BM - 1) / p.BM <= kSkMaxWg &&
-         gemm_w4_ok(M, N, K, K, K, N);
-}
-
-bool launch_w4_chain(int epi, const void* A, int lda, const void* B, void* C, int ldc, int M, int N, int K,
-                     const RopeEpi& re, hipStream_t st) {
-  if (M == 0) return true;
-  if (!w4_chain_ok(M, N, K) || !gemm_w4_ok(M, N, K, lda, K, ldc)) return false;
-  const Plan p = plan(M, N, K, false, 0, 0);
-  if (!run_w4(epi, (const uint16_t*)A, lda, (const uint16_t*)B, K, (uint16_t*)C, ldc, M, N, K, st, re, p.BM)) return false;
-  return true;
-}
-
-// Mid-M norm chain (rows in (decode_chain_max_m, 64], TP = 1): the decoder layer's two add +
-// RMSNorm launches (splitk_add_rmsnorm) fold into the planner's small-tile GEMMs.  O / down
-// (epi 0) split K and the tile's last split adds into the residual and leaves the row sums of
-// squares (mid_chain_finish); gate_up (epi 1, one K range) scales its accumulator rows by the
-// RMSNorm factor in its SiLU epilogue; QKV + RoPE (epi 3) takes the factor in the split-K slab
-// reduce of the RoPE + cache kernel, or in the weight-streaming kernel's row-scale prologue at
-// 5-8 rows (which computes it from the rows it streams).
-// gemm_mid_chain op: 0 off (default), 1 on (sc1 hand-off), 2 on (acquire hand-off).  Off by
-// default: the in-kernel finish adds ~3.5 us to each O / down call (two ticket round trips,
-// write-through partials, the band's row totals) against the ~5 us splitk_add_rmsnorm launch it
-// replaces, and the row scale costs gate_up ~0.8 us; interleaved on one box, batch 16 -1 % /
-// -3 % and batch 64 -2.6 % / -3.7 % (sc1 / acquire); without the band step (a timing probe,
-// numerics off) batch 16 +2-3 % and batch 64 -0.6 % (profiles/r06_mid_chain.md).
-static int g_mid_chain = 0;
-int gemm_mid_chain(int set) {
-  if (set >= 0) g_mid_chain = set;
-  return g_mid_chain;
-}
-
-bool mid_chain_ok(int M, int N, int K, int epi) {
-  if (!g_mid_chain || M <= decode_chain_max_m() || M > 64 || K % kBK || N % 128) return false;
-  int cus = 0;
-  if (!gemm_sk_available(&cus)) return false;
+// One GEMM of the norm chain (ops/__init__.py): op OP_CHAIN_RES_SS: C [M, N] += A . B^T in place
+// and ss <- the new rows' sums of squares; OP_CHAIN_RS / _SILU / _ROPE: epi(diag(rsqrt(ss / K +
+// eps)) . A . B^T) into C (RoPE: through re).  ss is an ss_buffer of the row width H (N for
+// RES_SS, K else): [M, H / 128] partials, then the [M] totals.  The decode forms (GEMV EPI_RES /
+// PRO_RS, weight-streaming kernel) take their row factors from the rows they stream and leave ss
+// alone; the mid form (planner tiles: the last split of a tile finishes, gate_up scales in its
+// SiLU epilogue) uses the totals only; the four-wave form both.  false: refused, nothing launched.
+bool launch_gemm_chain(int op, const void* A, int lda, const void* B, void* C, int ldc, int M, int N, int K,
+                       const RopeEpi& rope, float* ss, float eps, hipStream_t st) {
+  const PlanEnv env = gemm_live_env();
+  const Route rt = gemm_route(env, gemm_call(op, M, N, K, lda, K, ldc));
+  if (!rt.ok()) return false;
+  const bool res = op == OP_CHAIN_RES_SS;
+  const int epi = res ? EPI_NONE : op & 3;
+  RopeEpi re = epi == EPI_ROPE ? rope : RopeEpi{};
+  if (M <= decode_chain_max_m(env)) {
+    if (rt.family == FAM_GEMV && res) launch_gemv_res(A, lda, B, C, M, N, K, st);
+    else if (rt.family == FAM_GEMV) launch_gemv_rs(A, lda, B, C, ldc, M, N, K, epi, re, eps, st);
+    else if (res) launch_ws(A, lda, B, K, C, N, M, N, K, 5, false, re, 0.f, st);
+    else launch_ws(A, lda, B, K, C, ldc, M, N, K, epi, true, re, eps, st);
+    return true;
+  }
+  if (res) {
+    re.ss_out = ss;
+    re.ss_tot = ss + (size_t)M * (N / 128);
+  } else {
+    re.ss_in = ss + (size_t)M * (K / 128);
+    re.ss_inv_k = 1.f / (float)K;
+    re.ss_eps = eps;
+  }
+  if (rt.family == FAM_W4 || rt.family == FAM_W4H)
+    return run_w4(res ? 4 : epi | 8, (const uint16_t*)A, lda, (const uint16_t*)B, K, (uint16_t*)C, ldc, M, N, K, st, re, rt.BM);
+  // the mid chain
   if (epi == EPI_ROPE) {
-    if (ws_prefer(M, N, K, EPI_ROPE)) return K % 512 == 0;
-    const Plan p = rope_plan(M, N, K);
-    return !((p.BM == 256 || p.variant == 6) && p.BN >= 128) && rope_slabs_ok(p, M, N);
+    if (rt.family == FAM_WS) launch_ws(A, lda, B, K, nullptr, 0, M, N, K, 3, true, re, eps, st);
+    else run_rope_route(rt, A, lda, B, M, N, K, re, st);
+    return true;
   }
-  const Plan p = plan(M, N, K, false, 0, 0);
-  if (p.variant != 0 || p.BM > 64 || N % p.BN) return false;
-  if (epi == EPI_SILU_MUL) return p.splits == 1;
-  if (epi != EPI_NONE || p.splits < 2) return false;
-  const long gx = N / p.BN, gy = (M + p.BM - 1) / p.BM;
-  return gx * gy + gy <= kSkMaxWg &&
-         (size_t)p.splits * M * N + (size_t)M * gx <= (size_t)2 * kSkMaxWg * 256 * 256;
-}
-
-// residual [M, N] += A . B^T in place and ss_tot [M] <- the new rows' sums of squares (epi 0)
-bool launch_mid_res_ss(const void* A, int lda, const void* B, void* residual, int ldr, int M, int N, int K,
-                       float* ss_tot, hipStream_t st) {
-  if (M == 0) return true;
-  if (!mid_chain_ok(M, N, K, EPI_NONE)) return false;
-  float* ws = nullptr;
-  int* cnt = nullptr;
-  int cus = 0;
-  if (!gemm_sk_scratch(&ws, &cnt, &cus)) return false;
-  const Plan p = plan(M, N, K, false, 0, 0);
-  RopeEpi re{};
-  re.ss_cnt = cnt;
-  re.ss_tot = ss_tot;
-  re.mid_acq = g_mid_chain == 2;
-  launch_plan<EPI_NONE, false>(p, (const uint16_t*)A, lda, (const uint16_t*)B, K, (uint16_t*)residual, ldr, ws, M,
-                               N, K, nullptr, 0, st, re);
+  if (res) {
+    float* ws = nullptr;
+    int cus = 0;
+    RopeEpi fin{};
+    if (!gemm_sk_scratch(&ws, &fin.ss_cnt, &cus)) return false;
+    fin.ss_tot = re.ss_tot;
+    fin.mid_acq = env.mid_chain == 2;
+    launch_route<EPI_NONE, false>(rt, (const uint16_t*)A, lda, (const uint16_t*)B, K, (uint16_t*)C, ldc, ws, M, N, K,
+                                  nullptr, 0, st, fin);
+    return true;
+  }
+  RopeEpi rs{};
+  rs.ss_in = re.ss_in;
+  rs.ss_inv_k = re.ss_inv_k;
+  rs.ss_eps = eps;
+  launch_route<EPI_SILU_MUL, false>(rt, (const uint16_t*)A, lda, (const uint16_t*)B, K, (uint16_t*)C, ldc, nullptr, M,
+                                    N, K, nullptr, 0, st, rs);
   return true;
-}
-
-// out = SiLU-mul(diag(rsqrt(ss_tot / K + eps)) . A . B^T) (epi 1, gate_up)
-bool launch_mid_rs(const void* A, int lda, const void* B, void* out, int ldo, int M, int N, int K,
-                   const float* ss_tot, float eps, hipStream_t st) {
-  if (M == 0) return true;
-  if (!mid_chain_ok(M, N, K, EPI_SILU_MUL)) return false;
-  const Plan p = plan(M, N, K, false, 0, 0);
-  RopeEpi re{};
-  re.ss_in = ss_tot;
-  re.ss_inv_k = 1.f / (float)K;
-  re.ss_eps = eps;
-  launch_plan<EPI_SILU_MUL, false>(p, (const uint16_t*)A, lda, (const uint16_t*)B, K, (uint16_t*)out, ldo, nullptr,
-                                   M, N, K, nullptr, 0, st, re);
-  return true;
-}
-
-long gemm_workspace_floats(int M, int N, int K, int epi) {
-  if (gemv_takes(M, N, K, epi)) return 0;
-  const Plan p = plan(M, N, K, false, 0, 0);
-  return p.splits > 1 ? (long)p.splits * M * N : 0;
 }
 
 void launch_gemm(const void* A, int lda, const void* B, int ldb, void* C, int ldc, float* ws,
                  long ws_floats, int M, int N, int K, int epi, hipStream_t st) {
   if (M == 0) return;
-  if (gemv_takes(M, N, K, epi) && lda % 8 == 0 && ldb % 8 == 0) {
-    launch_gemv(A, lda, B, ldb, C, ldc, M, N, K, epi, st);
-    return;
-  }
-  Plan p = plan(M, N, K, false, 0, 0);
-  if (p.splits > 1 && (long)p.splits * M * N > ws_floats) { p.splits = 1; p.k_chunk = K; }
+  GemmCall c = gemm_call(epi, M, N, K, lda, ldb, ldc);
+  c.ws_avail = ws_floats;
+  const Route rt = gemm_route(gemm_live_env(), c);
+  if (rt.family == FAM_GEMV) return launch_gemv(A, lda, B, ldb, C, ldc, M, N, K, epi, st);
   if (epi == EPI_NONE)
-    launch_plan<EPI_NONE, false>(p, (const uint16_t*)A, lda, (const uint16_t*)B, ldb, (uint16_t*)C,
-                                 ldc, ws, M, N, K, nullptr, 0, st);
+    launch_route<EPI_NONE, false>(rt, (const uint16_t*)A, lda, (const uint16_t*)B, ldb, (uint16_t*)C,
+                                  ldc, ws, M, N, K, nullptr, 0, st);
   else
-    launch_plan<EPI_SILU_MUL, false>(p, (const uint16_t*)A, lda, (const uint16_t*)B, ldb,
-                                     (uint16_t*)C, ldc, ws, M, N, K, nullptr, 0, st);
-  if (p.splits > 1) {
-    const int outw = epi == EPI_NONE ? N : N / 2;
-    const long total = (long)M * (outw / 8);
-    const int g = (int)std::min<long>((total + 255) / 256, 4096);
-    if (epi == EPI_NONE)
-      splitk_reduce_kernel<EPI_NONE><<<g, 256, 0, st>>>((uint16_t*)C, ldc, ws, M, N, p.splits);
-    else
-      splitk_reduce_kernel<EPI_SILU_MUL><<<g, 256, 0, st>>>((uint16_t*)C, ldc, ws, M, N, p.splits);
-  }
+    launch_route<EPI_SILU_MUL, false>(rt, (const uint16_t*)A, lda, (const uint16_t*)B, ldb,
+                                      (uint16_t*)C, ldc, ws, M, N, K, nullptr, 0, st);
+  if (rt.finish == FIN_REDUCE) launch_splitk_reduce(epi, (uint16_t*)C, ldc, ws, M, N, rt.splits, st);
 }
 
 // y = A.B^T; residual += y; out = rmsnorm(residual) * w.  Returns false (nothing
@@ -1749,20 +1341,18 @@ bool launch_gemm_add_rmsnorm(const void* A, int lda, const void* B, void* out, v
                              const void* w, float eps, float* ws, long ws_floats, int M, int N,
                              int K, hipStream_t st) {
   if (M == 0) return true;
-  if (gemv_takes(M, N, K, EPI_NONE)) return false;  // decode sizes: GEMV + add_rmsnorm (or the norm chain)
-  if (ws_prefer(M, N, K, EPI_NONE) && lda % 8 == 0) {
-    // 5-16 rows of an O-size projection: the weight-streaming MFMA kernel adds into the residual
-    // in place (bf16(res + bf16(y)), norm.hip's rounding), then one RMSNorm pass
+  GemmCall c = gemm_call(OP_ADD_RMSNORM, M, N, K, lda, K, N);
+  c.ws_avail = ws_floats;
+  const Route rt = gemm_route(gemm_live_env(), c);
+  if (!rt.ok()) return false;
+  if (rt.family == FAM_WS) {
     launch_ws(A, lda, B, K, residual, N, M, N, K, 5, false, RopeEpi{}, 0.f, st);
     launch_rmsnorm(out, residual, w, eps, M, N, st);
     return true;
   }
-  int splits;
-  const Plan p = plan(M, N, K, false, 0, 0);
-  if (p.splits <= 1 || p.splits > kMaxSplits || (long)p.splits * M * N > ws_floats || N % 8) return false;
-  launch_plan<EPI_NONE, false>(p, (const uint16_t*)A, lda, (const uint16_t*)B, K, nullptr, N, ws,
-                               M, N, K, nullptr, 0, st);
-  splits = p.splits;
+  launch_route<EPI_NONE, false>(rt, (const uint16_t*)A, lda, (const uint16_t*)B, K, nullptr, N, ws,
+                                M, N, K, nullptr, 0, st);
+  const int splits = rt.splits;
   const int nvec = N / 8;
   int vpt = 1;
   while (vpt < 8 && nvec / vpt > 512) vpt <<= 1;
@@ -1784,49 +1374,26 @@ void launch_grouped_gemm(const void* A, const void* B, void* C, const int* offse
                          float** defer_ws, int* defer_splits) {
   if (defer_splits) *defer_splits = 1;
   if (M == 0) return;
-  if (a_rows == nullptr && defer_splits == nullptr && gemv_grouped_takes(M, N, K, epi)) {  // MoE decode: stream only the routed experts' weights
-    launch_gemv_grouped(A, B, C, offsets, n_groups, M, N, K, epi, st);
-    return;
-  }
-  Plan p = plan(M, N, K, true, n_groups, max_rows);
-  // Mid-size MoE batches (a few dozen rows per expert): one m-tile per expert x N/64 tiles
-  // is too few workgroups to stream every expert's weights at full rate (down at batch 64:
-  // 512 workgroups of K = 14336, 4.7 TB/s).  Split K like the dense path, partials in the
-  // stream-K slab buffer (same stream, so never in use by another launch), then the reduce
-  // kernel applies the epilogue.  Routed tiles are estimated as one m-tile per expert.
-  float* ws = nullptr;
-  if (p.variant != 3 && K >= 2048 && g_gp[3] != 1 && !(p.nosplit && g_gp[0] <= 0)) {
-    const SkBuf* b = sk_buf();
-    const long t_est = (long)((N + p.BN - 1) / p.BN) * std::max(1, std::min(n_groups, (M + p.BM - 1) / p.BM + n_groups));
-    constexpr int target = 1024;
-    int s = (int)std::min<long>(8, std::max<long>(1, target / std::max<long>(1, t_est)));
-    if (g_gp[3] > 1) s = g_gp[3];
-    while (s > 1 && (K / s) % kBK) --s;
-    if (b && s > 1 && (size_t)s * M * N * 4 <= (size_t)2 * kSkMaxWg * 256 * 256 * 4) {
-      p.splits = s;
-      p.k_chunk = K / s;
-      ws = b->ws;
-    }
-  }
+  GemmCall c = gemm_call(OP_GROUPED | epi, M, N, K, K, K, epi == EPI_NONE ? N : N / 2);
+  c.n_groups = n_groups, c.rows_per_group = max_rows;
+  c.indirect = a_rows != nullptr || defer_splits != nullptr;
+  const Route rt = gemm_route(gemm_live_env(), c);
+  if (rt.family == FAM_GEMV) return launch_gemv_grouped(A, B, C, offsets, n_groups, M, N, K, epi, st);
+  // split K: partials in the stream-K slab buffer (same stream, so never in use by another launch)
+  float* ws = rt.ws_src == WS_SRC_SCRATCH ? sk_buf()->ws : nullptr;
   RopeEpi re{};
   re.a_rows = a_rows;
   if (epi == EPI_NONE)
-    launch_plan<EPI_NONE, true>(p, (const uint16_t*)A, K, (const uint16_t*)B, K, (uint16_t*)C, N,
-                                ws, M, N, K, offsets, n_groups, st, re);
+    launch_route<EPI_NONE, true>(rt, (const uint16_t*)A, K, (const uint16_t*)B, K, (uint16_t*)C, N,
+                                 ws, M, N, K, offsets, n_groups, st, re);
   else
-    launch_plan<EPI_SILU_MUL, true>(p, (const uint16_t*)A, K, (const uint16_t*)B, K, (uint16_t*)C,
-                                    N / 2, ws, M, N, K, offsets, n_groups, st, re);
-  if (p.splits > 1 && defer_splits != nullptr && epi == EPI_NONE) {  // the caller sums the slabs
+    launch_route<EPI_SILU_MUL, true>(rt, (const uint16_t*)A, K, (const uint16_t*)B, K, (uint16_t*)C,
+                                     N / 2, ws, M, N, K, offsets, n_groups, st, re);
+  if (rt.finish == FIN_REDUCE && defer_splits != nullptr && epi == EPI_NONE) {  // the caller sums the slabs
     *defer_ws = ws;
-    *defer_splits = p.splits;
-  } else if (p.splits > 1) {
-    const int outw = epi == EPI_NONE ? N : N / 2;
-    const long total = (long)M * (outw / 8);
-    const int g = (int)std::min<long>((total + 255) / 256, 4096);
-    if (epi == EPI_NONE)
-      splitk_reduce_kernel<EPI_NONE><<<g, 256, 0, st>>>((uint16_t*)C, N, ws, M, N, p.splits);
-    else
-      splitk_reduce_kernel<EPI_SILU_MUL><<<g, 256, 0, st>>>((uint16_t*)C, N / 2, ws, M, N, p.splits);
+    *defer_splits = rt.splits;
+  } else if (rt.finish == FIN_REDUCE) {
+    launch_splitk_reduce(epi, (uint16_t*)C, epi == EPI_NONE ? N : N / 2, ws, M, N, rt.splits, st);
   }
 }
 

@@ -220,12 +220,6 @@ __global__ void __launch_bounds__(256) gemm_ws_kernel(const uint16_t* __restrict
   }
 }
 
-// rows the weight-streaming kernel takes, (gemv_chain_max_m, g_ws_max_m]: 0 = off (default, the
-// decode chain stays at the GEMV's 4 rows).  Measured slower than the planner's LDS-ring small
-// tiles on gate_up / down at every M and on all shapes at M >= 32 (profiles/r06_small_m_ws.md);
-// the gemm_ws_max_m op turns it on for A/B runs
-int g_ws_max_m = 0;
-
 // A/B plan of the sweep (gemm_ws_plan op, scripts/bench_ws.py): row blocks per workgroup (plain: 1 / 2 /
 // 4, SiLU-mul: 2 / 4; 0 = default 1 / 2), K-steps in flight (4 / 8; 0 = 8 where K allows) and
 // non-temporal (1) or cached (0, default: 64 B per row per load, the two halves of a line on
@@ -266,59 +260,10 @@ void run_ws(const uint16_t* A, int lda, const uint16_t* B, int ldb, uint16_t* C,
 
 }  // namespace
 
-int gemm_ws_max_m(int set) {
-  if (set >= 0) g_ws_max_m = set > 64 ? 64 : set;
-  return g_ws_max_m;
-}
-
-// Outside the chain, the plain decode projections take this kernel where it measured faster
-// than the planner's small tiles (profiles/r06_small_m_ws.md): the O-size (33 MB) and QKV-size
-// (50 MB) matrices at 5-8 rows.  Cold-weight microbench: o 8.4 vs 15.9 us, qkv 12.4 vs 17.8 (the
-// QKV form also does RoPE + the paged K/V stores, so the rope_cache slab reduce launch goes);
-// in the model the planner's O runs nearer 9 us, so end to end batch 8 gains 1.7 % and batch
-// 16 is within noise (-1 %): 8 rows.  gate_up / down and 32+ rows stay on the planner.  The
-// gemm_ws_small_m op (0 = off) is the A/B switch.
-int g_ws_small_m = 8;
-
-int gemm_ws_small_m(int set) {
-  if (set >= 0) g_ws_small_m = set > 64 ? 64 : set;
-  return g_ws_small_m;
-}
-
-// QKV + RoPE takes the weight-streaming kernel up to g_ws_rope_m rows (gemm_ws_rope_m op): it
-// replaces the planner's split-K tile AND the rope_cache slab-reduce launch after it
-int g_ws_rope_m = 8;
-int gemm_ws_rope_m(int set) {
-  if (set >= 0) g_ws_rope_m = set > 64 ? 64 : set;
-  return g_ws_rope_m;
-}
-
-bool ws_prefer(int M, int N, int K, int epi) {
-  if (M <= gemv_chain_max_m() || (long)N * K > 32L * 1024 * 1024 || K % 512) return false;
-  if (epi == WS_ROPE) return M <= g_ws_rope_m && N % 128 == 0;
-  return M <= g_ws_small_m && (epi == WS_NONE || epi == WS_RES) && N % 16 == 0;
-}
-
 void gemm_ws_plan(int rb, int u, int nt) {
   g_ws_rb = rb == 1 || rb == 2 || rb == 4 ? rb : 0;
   g_ws_u = u == 4 || u == 8 ? u : 0;
   g_ws_nt = nt != 0;
-}
-
-// Shapes this path takes: gemv_max_m() < M <= ws max (default 64), K a multiple of 512 (four K
-// quarters of whole 4-step rings), 16-B aligned rows, whole 16-row blocks (plain / residual),
-// whole 32-row gate / up groups (SiLU-mul), a QKV projection of 128-wide heads (RoPE).
-bool ws_takes(int M, int N, int K, int epi) {
-  if (M <= gemv_chain_max_m() || M > g_ws_max_m || K % 512 || N < 16) return false;
-  if (epi == WS_SILU_MUL) return N % 32 == 0;
-  if (epi == WS_ROPE) return N % 128 == 0;
-  return (epi == WS_NONE || epi == WS_RES) && N % 16 == 0;
-}
-
-int decode_chain_max_m() { return g_ws_max_m > gemv_chain_max_m() ? g_ws_max_m : gemv_chain_max_m(); }
-
-bool decode_chain_takes(int M, int N, int K, int epi) {
-  return M <= gemv_chain_max_m() ? gemv_chain_takes(M, N, K, epi) : ws_takes(M, N, K, epi);
 }
 
 void launch_ws(const void* A, int lda, const void* B, int ldb, void* C, int ldc, int M, int N, int K, int epi,

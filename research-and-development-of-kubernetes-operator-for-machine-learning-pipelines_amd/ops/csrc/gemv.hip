@@ -304,12 +304,6 @@ __global__ void __launch_bounds__(256) gemv_kernel(const uint16_t* __restrict__ 
   }
 }
 
-int gemv_max_m() {
-  // measured (scripts/history INDEX run38): the GEMV wins every decode projection at M <= 4 in
-  // the running model; at M = 8 the 64-row MFMA tiles stream gate_up / down faster
-  return 4;
-}
-
 // below this many row sets a workgroup's 4 waves share rows and split K (KW = 4): more loads
 // in flight per row.  Measured at batch-1/2/4 decode (scripts/run56.sh, run57.sh): at M <= 2
 // moving gate_up (7168 sets) to KW = 4 gives +3-4% tok/s at batch 1 and +1.5% at batch 2, at
@@ -364,16 +358,6 @@ void run_gemv(const uint16_t* A, int lda, const uint16_t* B, int ldb, uint16_t* 
 
 }  // namespace
 
-// Shapes this path takes: 1 <= M <= MLOP_GEMV_MAX_M (default 4, at most 8), 16-B aligned rows,
-// whole row pairs (EPI_NONE), whole 32-row gate/up groups (EPI_SILU_MUL), or a QKV
-// projection of 128-wide heads (EPI_ROPE: N = (Hq + 2 Hkv) * 128).
-bool gemv_takes(int M, int N, int K, int epi) {
-  if (M < 1 || M > gemv_max_m() || K % 8 || N < 4) return false;
-  if (epi == EPI_SILU_MUL) return N % 32 == 0;
-  if (epi == EPI_ROPE) return N % kHeadD == 0;
-  return epi == EPI_NONE && N % 4 == 0;
-}
-
 void launch_gemv(const void* A, int lda, const void* B, int ldb, void* C, int ldc, int M, int N, int K,
                  int epi, hipStream_t st) {
   auto* a = (const uint16_t*)A;
@@ -413,12 +397,6 @@ void run_gemv_grouped_m(const uint16_t* A, const uint16_t* B, uint16_t* C, int l
 #undef MLOP_GEMV_G
 }
 
-// MoE expert GEMMs at decode: M = routed rows in total (<= 8)
-bool gemv_grouped_takes(int M, int N, int K, int epi) {
-  return M >= 1 && M <= 8 && K % 8 == 0 && N % (epi == EPI_SILU_MUL ? 32 : 4) == 0 &&
-         (epi == EPI_NONE || epi == EPI_SILU_MUL);
-}
-
 void launch_gemv_grouped(const void* A, const void* B, void* C, const int* offsets, int n_groups, int M, int N,
                          int K, int epi, hipStream_t st) {
   auto* a = (const uint16_t*)A;
@@ -437,21 +415,11 @@ void launch_gemv_grouped(const void* A, const void* B, void* C, const int* offse
 #undef MLOP_GG
 }
 
-// The decode norm chain (M <= gemv_chain_max_m(), norm weights folded into the consuming projections:
+// The decode norm chain (M <= PlanEnv::gemv_chain_max_m, gemm_plan.h; norm weights folded into the consuming projections:
 // LlamaModel.fold_norms): O and down add their output into the residual in place (EPI_RES),
 // QKV and gate_up read the raw residual and scale each row's sums by rsqrt(mean(a^2) + eps)
 // taken from the chunks they stream anyway (PRO_RS).  A decode layer is then five launches
 // and no add + RMSNorm pass: the GEMV form of gemm_w4.hip's large-M chain (W4_ADD_SS / W4_RS).
-// rows the chain's GEMV form takes (above gemv_max_m() the GEMV takes nothing anyway).
-// Measured (scripts/history INDEX r4_chain8): the GEMV with the chain at 6 / 8 rows streams
-// 1,419 / 1,612 tok/s against the MFMA path's 1,522 / 1,936 (its split-K reduce already
-// carries the add + RMSNorm), so 4 stays.
-int gemv_chain_max_m() { return 4; }
-
-bool gemv_chain_takes(int M, int N, int K, int epi) {
-  return M <= gemv_chain_max_m() && gemv_takes(M, N, K, epi);
-}
-
 void launch_gemv_rs(const void* A, int lda, const void* B, void* C, int ldc, int M, int N, int K, int epi,
                     const RopeEpi& re, float eps, hipStream_t st) {
   auto* a = (const uint16_t*)A;

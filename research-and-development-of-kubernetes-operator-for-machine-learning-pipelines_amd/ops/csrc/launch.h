@@ -50,7 +50,7 @@ struct RopeEpi {
   const int* slots;
   int Hq, Hkv, BS;
   // four-wave norm chain (run_w4 only; the large-M TP=1 decoder with unit norm weights, see
-  // launch_w4_chain).  Producer (C += A.B^T): ss_out = [M, N / 128] partial sums of squares of
+  // launch_gemm_chain).  Producer (C += A.B^T): ss_out = [M, N / 128] partial sums of squares of
   // the updated residual rows (one per row and wave column block), then ss_tot [M] = their row
   // sums, added in a fixed order by the last tile of each 256-row band (ss_cnt: one ticket per
   // band).  Consumer: ss_in = a producer's ss_tot; the accumulators of row r are scaled by
@@ -76,45 +76,27 @@ struct RopeEpi {
 // RoPE + paged-cache stores from the QKV projection's fp32 split-K slabs ws[splits][T][N] (the
 // split-K reduce fused in: small-M launch_gemm_rope)
 void launch_rope_cache_slabs(const RopeEpi& re, const float* ws, int splits, int T, int N, hipStream_t st);
-long gemm_workspace_floats(int M, int N, int K, int epi);
-// large-M kernel variant of the GEMM planner (gemm.hip plan(): 0 256x128, 1/2 256x256
-// 8-wave, 3 ping-pong, 5 four-wave asm K-loop); set >= 0 overrides (in-process A/B), returns the current value
-int gemm_big_variant(int set);
-int gemm_half_tile(int set);
-int gemm_grouped_narrow(int set);
-void gemm_grouped_plan(int bm, int bn, int stages, int splits);
-void gemm_dense_plan(int variant, int bm, int bn, int splits, int stages = 0);
-// variant 5: the four-wave hand-scheduled 256x256 kernel (gemm_w4.hip), variant 6 its 128x256
-// half-height tile; epi 0 / 1 / 3
-bool gemm_w4_ok(int M, int N, int K, int lda, int ldb, int ldc = 0);
-// the four-wave kernel cuts its r = T % CUs tail tiles into K-halves (2r <= CUs, nk even)
-bool gemm_w4_split_ok(int T, int nk);
+// The GEMM planner's knobs, predicates and queries (gemm_big_variant, gemm_dense_plan, gemv_takes,
+// gemm_rope_supported, w4_chain_ok, ...) are declared in gemm_plan.h.
 bool gemm_sk_scratch(float** ws, int** cnt, int* cus);
 bool gemm_sk_available(int* cus);
 bool run_w4(int epi, const uint16_t* A, int lda, const uint16_t* B, int ldb, uint16_t* C, int ldc, int M, int N,
             int K, hipStream_t st, const RopeEpi& re, int bm = 256);
-// norm chain on the four-wave kernel (epi flags: 4 = C += A.B^T with ss partials, 8 = rows scaled
-// by re.ss_in; 4, 0|8, 1|8, 3|8 are built): true when every such GEMM of this shape runs there
-bool w4_chain_ok(int M, int N, int K);
-bool launch_w4_chain(int epi, const void* A, int lda, const void* B, void* C, int ldc, int M, int N, int K,
-                     const RopeEpi& re, hipStream_t st);
-int gemm_small_stages(int set);  // LDS-DMA ring depth of the M <= 128 tiles (3, or 5/6)
-int gemm_small_tile(int set);    // M <= 64 tiles: 0 = 64 x 64, 32 / 64 = row-fitted BM x BN
+// one GEMM of the norm chain (op: gemm_plan.h OP_CHAIN_*; epi flags of the four-wave form: 4 = C +=
+// A.B^T with ss partials, 8 = rows scaled by ss; 4, 0|8, 1|8, 3|8 are built), on the form the
+// planner names for its row count; false = refused, nothing launched
+bool launch_gemm_chain(int op, const void* A, int lda, const void* B, void* C, int ldc, int M, int N, int K,
+                       const RopeEpi& rope, float* ss, float eps, hipStream_t st);
 // non-temporal weight loads of the one-m-tile gemm_kernel launches: bit 0 dense, bit 1 grouped,
 // bit 2 the grouped ping-pong kernel
 int gemm_small_nt(int set);
 // non-temporal K / V page loads of the decode attention kernel
 int attn_kv_nt(int set);
 int gemm_slab_nt(int set);
-int gemm_rope_split(int set);
-int gemm_split_target(int set);  // K ranges of the small-M QKV + RoPE launch (A/B)
-// stream-K tail of the ping-pong GEMM: mode (1 on, 0 off; set >= 0 changes it) and the
-// per-device partial / counter buffers (allocate once, outside graph capture)
-int gemm_sk_mode(int set);
+// the stream-K scratch of the ping-pong GEMM's tail (and of every other split-K slab / ticket
+// user): per-device partial / counter buffers (allocate once, outside graph capture)
 bool gemm_sk_reserve();
-int gemm_sk_workgroups(int M, int N, int K);
 // K2 skinny GEMV (gemv.hip): decode projections at M <= 8 (epi 0 none, 1 silu-mul, 3 rope)
-bool gemv_takes(int M, int N, int K, int epi);
 void launch_gemv(const void* A, int lda, const void* B, int ldb, void* C, int ldc, int M, int N, int K,
                  int epi, hipStream_t st);
 void launch_gemv_rope(const void* A, int lda, const void* B, int M, int N, int K, const RopeEpi& re,
@@ -125,40 +107,17 @@ struct NormPro {
 };
 // decode norm chain (gemv.hip PRO_RS / EPI_RES, M <= 4): C = epi(rowscale(A) . B^T) with
 // rowscale = rsqrt(mean(A_row^2) + eps) (norm weights folded into B); residual += A . B^T
-bool gemv_chain_takes(int M, int N, int K, int epi);
-// weight-streaming MFMA GEMM (gemm_ws.hip) at gemv_chain_max_m() < M <= gemm_ws_max_m() (64):
+// weight-streaming MFMA GEMM (gemm_ws.hip) at gemv_chain_max_m < M <= gemm_ws_max_m (64):
 // epi 0 plain, 1 SiLU-mul, 3 RoPE + paged K/V (re), 5 residual += (C in place); rs: A is the raw
 // residual, rows scaled by rsqrt(mean(a^2) + eps) (norm weights folded into B)
-bool ws_takes(int M, int N, int K, int epi);
-int gemm_ws_max_m(int set);
 void gemm_ws_plan(int rb, int u, int nt);
-int gemm_ws_small_m(int set);
-int gemm_ws_rope_m(int set);  // rows up to which QKV + RoPE takes the weight-streaming kernel
-// the plain (non-chain) decode projections this kernel takes instead of the planner
-bool ws_prefer(int M, int N, int K, int epi);
-// mid-M norm chain on the planner's small tiles (gemm.hip): epi 0 = O / down (split-K, the
-// last split adds into the residual and leaves the row sums of squares), 1 = gate_up (SiLU-mul,
-// row-scaled), 3 = QKV + RoPE (row-scaled slab reduce, or the ws kernel at 5-8 rows)
-int gemm_mid_chain(int set);
-bool mid_chain_ok(int M, int N, int K, int epi);
-bool launch_mid_res_ss(const void* A, int lda, const void* B, void* residual, int ldr, int M, int N, int K,
-                       float* ss_tot, hipStream_t st);
-bool launch_mid_rs(const void* A, int lda, const void* B, void* out, int ldo, int M, int N, int K,
-                   const float* ss_tot, float eps, hipStream_t st);
-// the decode norm chain's forms: the GEMV up to gemv_chain_max_m() rows, then the weight-
-// streaming MFMA kernel up to gemm_ws_max_m()
-int decode_chain_max_m();
-bool decode_chain_takes(int M, int N, int K, int epi);
 void launch_ws(const void* A, int lda, const void* B, int ldb, void* C, int ldc, int M, int N, int K, int epi,
                bool rs, const RopeEpi& re, float eps, hipStream_t st);
-int gemv_chain_max_m();
 void launch_gemv_rs(const void* A, int lda, const void* B, void* C, int ldc, int M, int N, int K, int epi,
                     const RopeEpi& re, float eps, hipStream_t st);
 void launch_gemv_res(const void* A, int lda, const void* B, void* residual, int M, int N, int K, hipStream_t st);
-bool gemv_grouped_takes(int M, int N, int K, int epi);
 void launch_gemv_grouped(const void* A, const void* B, void* C, const int* offsets, int n_groups, int M, int N,
                          int K, int epi, hipStream_t st);
-bool gemm_rope_supported(int M, int N, int K);
 bool launch_gemm_rope(const void* A, int lda, const void* B, int M, int N, int K, const RopeEpi& re,
                       hipStream_t st);
 void launch_gemm(const void* A, int lda, const void* B, int ldb, void* C, int ldc, float* ws,

@@ -1066,3 +1066,101 @@ def test_gemm_ws_vs_fp32(gpu, ws_on, plan, M, N, K, epi):
     out2 = torch.empty_like(out[:M])
     torch.ops.mlop.gemm_ws(out2, a, w, epi, False, 0.0)
     assert torch.equal(out2, out[:M])
+
+
+# ---- the GEMM planner (ops/csrc/gemm_plan.cc; its routes are pinned on the CPU by test_gemm_plan_cpu.py) ----
+ROUTE_FIELDS = ("family", "tile", "BM", "BN", "WM", "WN", "stages", "setprio", "splits", "k_chunk", "m_tiles",
+                "sk_d", "sk_wgs", "finish", "ws_src", "ws_floats")  # gemm_plan.h gemm_route_fields
+OP_PLAIN, OP_SILU, OP_ADD_NORM, OP_ROPE, OP_GROUPED = 0, 1, 2, 3, 16  # gemm_plan.h GemmOp
+
+
+def test_gemm_route_live_matches_pure(gpu):
+    """The route the launchers execute on this device (gemm_route: the knobs + the device's CU
+    count and reserved scratch) is the pure planner's for the same two facts given explicitly
+    (gemm_route_env), over the headline projections.  Nothing is launched."""
+    ops._sk_reserve(torch.device(gpu))
+    cus = min(torch.cuda.get_device_properties(gpu).multi_processor_count, 256)
+    H, I = 4096, 14336
+    qkv, o, gate_up, down = (6144, H), (H, H), (2 * I, H), (H, I)
+    cases = [(6, *qkv, OP_ROPE), (16, *qkv, OP_ROPE), (2048, *qkv, OP_ROPE), (1024, *o, OP_PLAIN),
+             (2048, *o, OP_ADD_NORM), (768, *down, OP_PLAIN), (4608, *down, OP_ADD_NORM),
+             (64, *gate_up, OP_SILU), (4088, *gate_up, OP_SILU)]
+    for M, N, K, op in cases:
+        live = list(torch.ops.mlop.gemm_route(M, N, K, op))
+        assert len(live) == len(ROUTE_FIELDS)
+        assert live == list(torch.ops.mlop.gemm_route_env(M, N, K, op, cus, True)), (M, N, K, op)
+    assert dict(zip(ROUTE_FIELDS, torch.ops.mlop.gemm_route(6, *qkv, OP_ROPE)))["family"] == 2   # weight-streaming
+    assert dict(zip(ROUTE_FIELDS, torch.ops.mlop.gemm_route(4088, *gate_up, OP_SILU)))["family"] == 5  # four-wave
+    # Mixtral grouped down at 128 routed rows over 8 experts
+    g = (128, H, I, OP_GROUPED)
+    assert list(torch.ops.mlop.gemm_route(*g, 8, 16)) == list(torch.ops.mlop.gemm_route_env(*g, cus, True, 8, 16))
+    # without the scratch nothing may name it
+    r = dict(zip(ROUTE_FIELDS, torch.ops.mlop.gemm_route_env(16, *qkv, OP_ROPE, cus, False)))
+    assert r["family"] == 0 and r["ws_src"] == 0
+
+
+def test_gemm_every_tile_config(gpu):
+    """Every entry of the tile table (gemm_tile_configs), dense and grouped, forced through the
+    gemm_dense_plan / gemm_grouped_plan overrides at M = BM + 3 ragged rows (grouped: 3 experts
+    of BM + 3, 0 and 5 rows), N = 512, K = 1024, no epilogue: the route must name exactly that
+    entry and the result must match the fp32 product.  A wrong table row, (WM, WN) or ring depth
+    gives wrong numbers or a refused launch here.  Not reachable by an override: the dense 256 x
+    256 setprio tile (large-M variant 2: run through gemm_big_variant at 2048 + 3 rows instead)
+    and the grouped 256 x 256 tiles (a grouped 256 x 256 plan is the ping-pong kernel's)."""
+    torch.manual_seed(11)
+    dev = torch.device(gpu)
+    ops._sk_reserve(dev)
+    flat = list(torch.ops.mlop.gemm_tile_configs())
+    tiles = [tuple(flat[i:i + 7]) for i in range(0, len(flat), 7)]
+    assert len(tiles) == 20 and len(set(tiles)) == 20
+    N, K = 512, 1024
+    w = (0.05 * torch.randn(3, N, K, device=gpu)).to(bf)
+    prev_stages = torch.ops.mlop.gemm_small_stages(-1)
+    prev_big = torch.ops.mlop.gemm_big_variant(-1)
+    prev_backend = ops.GEMM_BACKEND
+    ops.GEMM_BACKEND = "mlop"
+    seen = []
+    try:
+        for idx, (BM, BN, WM, WN, stages, prio, rope) in enumerate(tiles):
+            # the 128-row tile takes its ring depth from gemm_small_stages, the others from the plan
+            torch.ops.mlop.gemm_small_stages(stages if BM == 128 else prev_stages)
+            # dense
+            M = BM + 3
+            if (BM, BN) == (256, 256) and prio:
+                M = 2048 + 3
+                torch.ops.mlop.gemm_big_variant(2)
+            elif (BM, BN) == (256, 256):
+                torch.ops.mlop.gemm_dense_plan(1, -1, -1, -1, 0)
+            else:
+                torch.ops.mlop.gemm_dense_plan(0, BM, BN, -1, stages)
+            r = dict(zip(ROUTE_FIELDS, torch.ops.mlop.gemm_route(M, N, K, OP_PLAIN)))
+            assert r["family"] == 3 and r["tile"] == idx, (idx, tiles[idx], r)
+            assert (r["BM"], r["BN"], r["WM"], r["WN"], r["stages"], r["setprio"]) == (BM, BN, WM, WN, stages, prio)
+            x = torch.randn(M, K, device=gpu, dtype=bf)
+            close(ops.gemm(x, w[0]), x.float() @ w[0].float().t())
+            torch.ops.mlop.gemm_dense_plan(-1, -1, -1, -1, 0)
+            torch.ops.mlop.gemm_big_variant(prev_big)
+            seen.append(("dense", idx))
+            # grouped
+            if (BM, BN) == (256, 256):
+                continue
+            rows = [BM + 3, 0, 5]
+            off = torch.tensor([0] + list(np.cumsum(rows)), device=gpu, dtype=torch.int32)
+            R = sum(rows)
+            torch.ops.mlop.gemm_grouped_plan(BM, BN, stages, -1)
+            r = dict(zip(ROUTE_FIELDS, torch.ops.mlop.gemm_route(R, N, K, OP_GROUPED, 3, BM + 3)))
+            assert r["family"] == 3 and r["tile"] == idx, (idx, tiles[idx], r)
+            xg = torch.randn(R, K, device=gpu, dtype=bf)
+            y = ops.grouped_gemm(xg, w, off, avg_rows=BM + 3)
+            torch.ops.mlop.gemm_grouped_plan(-1, -1, -1, -1)
+            for e in (0, 2):
+                a, b = int(off[e]), int(off[e + 1])
+                close(y[a:b], xg[a:b].float() @ w[e].float().t())
+            seen.append(("grouped", idx))
+    finally:
+        torch.ops.mlop.gemm_dense_plan(-1, -1, -1, -1, 0)
+        torch.ops.mlop.gemm_grouped_plan(-1, -1, -1, -1)
+        torch.ops.mlop.gemm_small_stages(prev_stages)
+        torch.ops.mlop.gemm_big_variant(prev_big)
+        ops.GEMM_BACKEND = prev_backend
+    assert len(seen) == 20 + 18

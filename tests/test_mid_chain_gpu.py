@@ -1,5 +1,5 @@
 """Mid-M norm chain (5-64 rows, the canary's concurrency regime) on the planner's small tiles
-(gemm.hip mid_chain_ok / launch_mid_res_ss / launch_mid_rs, rope_cache.hip's row-scaled slab
+(gemm_plan.cc mid_chain_ok, gemm.hip launch_gemm_chain, rope_cache.hip's row-scaled slab
 reduce): O / down split K and the tile's last split adds into the residual and leaves the row
 sums of squares, gate_up / QKV scale their rows by the RMSNorm factor, so a decoder layer has no
 add + RMSNorm launch.  Checked against the fp32 oracle and, for the residual, bit for bit against
