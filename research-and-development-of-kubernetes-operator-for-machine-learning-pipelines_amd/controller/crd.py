@@ -101,6 +101,8 @@ class ModelSpec:
     max_num_seqs: int | None = None
     kv_target_fraction: float | None = None
     canary: CanaryPolicy = field(default_factory=CanaryPolicy)
+    # LoRA adapters served beside the base model by the LLM runtime: ((name, uri), ...)
+    adapters: tuple = ()
 
     @classmethod
     def from_spec(cls, spec: dict) -> "ModelSpec":
@@ -114,7 +116,9 @@ class ModelSpec:
                    replicas=int(spec.get("replicas", 1)),
                    max_model_len=spec.get("maxModelLen"), max_num_seqs=spec.get("maxNumSeqs"),
                    kv_target_fraction=spec.get("kvTargetFraction"),
-                   canary=CanaryPolicy.from_spec(spec))
+                   canary=CanaryPolicy.from_spec(spec),
+                   adapters=tuple((a.get("name"), a.get("uri")) for a in (spec.get("adapters") or [])
+                                  if isinstance(a, dict)))
 
     def validate(self) -> list[str]:
         errs = []
@@ -124,6 +128,15 @@ class ModelSpec:
             errs.append("spec.modelAlias is required")
         if self.monitoring_interval <= 0:
             errs.append("spec.monitoringInterval must be > 0")
+        if self.adapters:
+            names = [n for n, _ in self.adapters]
+            if any(not n or not u for n, u in self.adapters):
+                errs.append("spec.adapters entries need a name and a uri")
+            if len(set(names)) != len(names):
+                errs.append("spec.adapters names must be unique")
+            if int(self.tensor_parallel or 1) > 1 or int(self.expert_parallel or 1) > 1:
+                errs.append("spec.adapters needs tensorParallel = 1 and expertParallel = 1 "
+                            "(LoRA adapters are not sharded)")
         return errs
 
 

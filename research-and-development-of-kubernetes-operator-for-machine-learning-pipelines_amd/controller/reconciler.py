@@ -286,7 +286,8 @@ class MlflowModelReconciler:
                 v, uri, spec.minio_secret, traffic, runtime=runtime, replicas=spec.replicas, placement=placement,
                 image=self.settings.runtime_image, gpu_resource=self.settings.gpu_resource,
                 model_name=spec.model_name, deployment=md["name"], namespace=md["namespace"],
-                architecture=arch, engine_args=engine_args))
+                architecture=arch, engine_args=engine_args,
+                adapters=spec.adapters if runtime == seldon.RUNTIME_LLM else None))
         self.placement_notes[(md["namespace"], md["name"])] = notes
         return seldon.build_seldon_deployment(md["name"], md["namespace"], body, preds)
 

@@ -18,6 +18,7 @@ Predictor runtimes:
 from __future__ import annotations
 
 import copy
+import json
 
 from .crd import API_VERSION, KIND, SELDON_GROUP, SELDON_KIND, SELDON_VERSION
 
@@ -47,7 +48,7 @@ def build_predictor(version, model_uri: str, secret: str | None, traffic: int, r
                     replicas: int = 1, placement: dict | None = None, image: str = "mlopamd/runtime-rocm:0.1.0",
                     gpu_resource: str = "amd.com/gpu", model_name: str | None = None,
                     deployment: str = "", namespace: str = "", architecture: str | None = None,
-                    engine_args: dict | None = None) -> dict:
+                    engine_args: dict | None = None, adapters=None) -> dict:
     graph = {"name": graph_name(version), "modelUri": model_uri, "envSecretRefName": secret, "children": []}
     pred = {"graph": graph, "name": predictor_name(version), "replicas": int(replicas), "traffic": int(traffic)}
     if runtime == RUNTIME_STOCK:
@@ -76,6 +77,10 @@ def build_predictor(version, model_uri: str, secret: str | None, traffic: int, r
         env.append({"name": "MLOP_ARCHITECTURE", "value": architecture})
     for k, v in (engine_args or {}).items():
         env.append({"name": f"MLOP_ENGINE_{k.upper()}", "value": str(v)})
+    if adapters:  # LoRA adapters the runtime loads before ready (runtime/server.py load_env_adapters)
+        env.append({"name": "MLOP_ADAPTERS",
+                    "value": json.dumps([{"name": n, "uri": u} for n, u in adapters], separators=(",", ":"))})
+        env.append({"name": "MLOP_ENGINE_MAX_ADAPTERS", "value": str(len(adapters))})
     container = {
         "name": graph_name(version),
         "image": image,

@@ -99,11 +99,18 @@ class LlamaModel:
         post_norm -> gate_up: W[:, k] *= g[k]) and set the norm weights to ones, so the large-M
         forward can apply the normalisation as a per-row factor after the GEMM (norm chain).
         The same function up to the bf16 rounding of g * W."""
-        for L in self.layers:
+        # the folded weights stay available (a few KB per layer): a LoRA adapter loaded later
+        # needs the same fold on the A matrices that read the normalised input (models/lora.py)
+        prev = getattr(self, "folded_norms", None)
+        kept = []
+        for i, L in enumerate(self.layers):
+            kept.append({})
             for norm, proj in self._folds():
                 g = L[norm].float()
+                kept[i][norm] = g.clone() if prev is None else prev[i][norm] * g
                 L[proj].copy_((L[proj].float() * g[None, :]).to(L[proj].dtype))
                 L[norm].fill_(1)
+        self.folded_norms = kept
         self.unit_norms = all(bool((L[k] == 1).all()) for L in self.layers for k in ("in_norm", "post_norm"))
         return self
 
@@ -151,9 +158,12 @@ class LlamaModel:
     def weight_bytes(self) -> int:
         return sum(t.numel() * t.element_size() for t in self.weight_tensors())
 
-    def forward(self, ids: torch.Tensor, meta, kv) -> torch.Tensor:
+    def forward(self, ids: torch.Tensor, meta, kv, lora=None) -> torch.Tensor:
         """ids [T] int64; meta: AttnMeta (positions/slots/tables); kv: KVCache.
-        Returns the final-normed hidden states of every token [T, H]."""
+        Returns the final-normed hidden states of every token [T, H].  ``lora``: a
+        ``models.lora.LoraStep`` when some token of the step uses an adapter."""
+        if lora is not None:
+            return self._forward_lora(ids, meta, kv, lora)
         cfg, tp = self.cfg, self.ps.tp
         eps = cfg.rms_eps
         h = ops.embedding(ids, self.embed, self.vocab_start)
@@ -191,6 +201,34 @@ class LlamaModel:
             # communication stream under the GEMM of chunk i+1 (parallel/overlap.py)
             x = row_parallel_add_norm(a.view(a.shape[0], -1), L["o"], tp, residual, L["post_norm"], eps)
             x = self.mlp_row_parallel(i, x, residual, nxt, eps)
+        return x
+
+    def _forward_lora(self, ids, meta, kv, lora) -> torch.Tensor:
+        """The multi-LoRA forward (TP = 1): the layer from its unfused blocks, each projection
+        followed by the per-token low-rank delta B[slot] . (A[slot] . x) (ops.lora_shrink /
+        lora_expand_add) before the next non-linearity.  Rows without an adapter (slot -1) ride
+        along; the expand does not touch them."""
+        assert self.ps.tp.size == 1, "LoRA adapters are served at TP = 1"
+        eps = self.cfg.rms_eps
+        ts, rank = lora.tok_slot, lora.slot_rank
+
+        def proj(x, L, S, name):
+            y = ops.gemm(x, L[name])
+            A, B, tile_group, G = S[name]
+            return ops.lora_expand_add(y, ops.lora_shrink(x, A, ts, rank, groups=G), B, tile_group, ts, rank)
+
+        residual = ops.embedding(ids, self.embed, self.vocab_start)
+        x = ops.rmsnorm(residual, self.layers[0]["in_norm"], eps)
+        for i, (L, S) in enumerate(zip(self.layers, lora.layers)):
+            qkv = proj(x, L, S, "qkv")
+            q = ops.rope_cache(qkv, meta.positions, self.cos_sin, meta.slots, kv.k[i], kv.v[i], self.n_q)
+            a = ops.paged_attention(q, kv.k[i], kv.v[i], meta)
+            o = proj(a.view(a.shape[0], -1), L, S, "o")
+            x = ops.add_rmsnorm(o, residual, L["post_norm"], eps)
+            act = ops.silu_mul(proj(x, L, S, "gate_up"), interleaved=True)
+            d = proj(act, L, S, "down")
+            nxt = self.layers[i + 1]["in_norm"] if i + 1 < len(self.layers) else self.final_norm
+            x = ops.add_rmsnorm(d, residual, nxt, eps)
         return x
 
     def mlp_row_parallel(self, i, x, residual, next_norm, eps):

@@ -35,7 +35,21 @@ from .config import ModelConfig, PRESETS
 _ARCH_NAMES = {"LlamaForCausalLM": "llama", "MixtralForCausalLM": "mixtral", "MistralForCausalLM": "llama"}
 
 
-def resolve_model_dir(uri: str | None) -> Path | None:
+def _is_checkpoint(d: Path) -> bool:
+    return (d / "config.json").is_file() and any(d.glob("*.safetensors"))
+
+
+def _is_adapter(d: Path) -> bool:
+    return (d / "adapter_config.json").is_file()
+
+
+def resolve_adapter_dir(uri: str | None) -> Path | None:
+    """Local PEFT adapter directory for an adapter URI (the rules of ``resolve_model_dir``,
+    with ``adapter_config.json`` as the marker file), or None."""
+    return resolve_model_dir(uri, _is_adapter)
+
+
+def resolve_model_dir(uri: str | None, marker=_is_checkpoint) -> Path | None:
     """Local checkpoint directory for a model URI, or None (serve random-init weights)."""
     if not uri:
         return None
@@ -51,7 +65,7 @@ def resolve_model_dir(uri: str | None) -> Path | None:
     else:
         p = Path(uri)
     for cand in (p, p / "model", p / "checkpoint", p / "artifacts"):
-        if (cand / "config.json").is_file() and any(cand.glob("*.safetensors")):
+        if marker(cand):
             return cand
     return None
 
@@ -213,3 +227,92 @@ def known_preset(cfg: ModelConfig) -> str | None:
                    max_position=cfg.max_position) == cfg:
             return n
     return None
+
+
+# ---------------------------------------------------------------- LoRA --
+
+_LORA_KEY = "base_model.model.model.layers.{i}.{blk}.{m}.lora_{ab}.weight"
+_LORA_BLOCK = {"q_proj": "self_attn", "k_proj": "self_attn", "v_proj": "self_attn", "o_proj": "self_attn",
+               "gate_proj": "mlp", "up_proj": "mlp", "down_proj": "mlp"}
+
+
+def _adapter_digest(path: Path) -> bytes:
+    import hashlib
+
+    h = hashlib.blake2b(digest_size=16)
+    for f in sorted(path.glob("adapter_config.json")) + sorted(path.glob("*.safetensors")):
+        h.update(f.name.encode())
+        with open(f, "rb") as fh:
+            for chunk in iter(lambda: fh.read(1 << 20), b""):
+                h.update(chunk)
+    return h.digest()
+
+
+def load_adapter(path: str | os.PathLike, cfg: ModelConfig, max_rank: int | None = None):
+    """Read a PEFT-format LoRA adapter directory (``adapter_config.json`` +
+    ``adapter_model.safetensors``) into our layout: ``models.lora.Adapter``.  Settings this
+    runtime cannot serve raise ValueError (they would otherwise give wrong logits silently)."""
+    import math
+
+    from ..ops import interleave_gate_up
+    from .lora import MAX_LORA_RANK, PROJ_MODULES, TARGET_MODULES, Adapter, check_shapes, module_shapes
+
+    path = Path(path)
+    if not (path / "adapter_config.json").is_file():
+        raise ValueError(f"{path} holds no adapter_config.json")
+    ac = json.loads((path / "adapter_config.json").read_text())
+    if cfg.is_moe:
+        raise ValueError("LoRA adapters are served on dense Llama / Mistral models only (not Mixtral)")
+    check_shapes(cfg)
+    if str(ac.get("peft_type", "LORA")).upper() != "LORA":
+        raise ValueError(f"unsupported peft_type {ac.get('peft_type')!r} (only LORA)")
+    if ac.get("use_dora"):
+        raise ValueError("DoRA adapters (use_dora) are not supported")
+    if ac.get("bias", "none") != "none":
+        raise ValueError(f"bias={ac.get('bias')!r} is not supported (only 'none')")
+    if ac.get("modules_to_save"):
+        raise ValueError(f"modules_to_save={ac['modules_to_save']} is not supported")
+    for k in ("rank_pattern", "alpha_pattern"):
+        if ac.get(k):
+            raise ValueError(f"a non-empty {k} is not supported (one rank / alpha per adapter)")
+    r = int(ac["r"])
+    cap = MAX_LORA_RANK if max_rank is None else min(MAX_LORA_RANK, int(max_rank))
+    if r < 1 or r > cap:
+        raise ValueError(f"adapter rank {r} is outside [1, {cap}] (the maximum LoRA rank)")
+    tm = ac.get("target_modules")
+    if isinstance(tm, str) or not tm:
+        raise ValueError(f"target_modules must be a list of module names, got {tm!r}")
+    bad = sorted(set(tm) - set(TARGET_MODULES))
+    if bad:
+        raise ValueError(f"unsupported target_modules {bad} (embedding / lm_head and other layers cannot take "
+                         f"an adapter; supported: {list(TARGET_MODULES)})")
+    alpha = float(ac.get("lora_alpha", r))
+    scale = alpha / math.sqrt(r) if ac.get("use_rslora") else alpha / r
+    t = _Tensors(path)
+    shapes = module_shapes(cfg)
+    known = set()
+    layers = []
+    for i in range(cfg.num_layers):
+        per = {}
+        for m in tm:
+            ka, kb = (_LORA_KEY.format(i=i, blk=_LORA_BLOCK[m], m=m, ab=ab) for ab in "AB")
+            known.update((ka, kb))
+            a, b = t.get(ka).float(), t.get(kb).float()
+            n, k = shapes[m]
+            if tuple(a.shape) != (r, k) or tuple(b.shape) != (n, r):
+                raise ValueError(f"layer {i} {m}: lora_A {tuple(a.shape)} / lora_B {tuple(b.shape)} do not fit "
+                                 f"rank {r} and the base weight [{n}, {k}]")
+            per[m] = (a, b * scale)  # the scaling in fp32; one rounding when the slot is filled
+        L = {}
+        for proj, mods in PROJ_MODULES.items():
+            if not any(m in per for m in mods):
+                continue
+            K = shapes[mods[0]][1]
+            A = torch.stack([per[m][0] if m in per else torch.zeros(r, K) for m in mods])
+            Bs = [per[m][1] if m in per else torch.zeros(shapes[m][0], r) for m in mods]
+            L[proj] = (A, interleave_gate_up(*Bs) if proj == "gate_up" else torch.cat(Bs, 0))
+        layers.append(L)
+    extra = sorted(k for k in t._where if k not in known)
+    if extra:
+        raise ValueError(f"adapter holds tensors outside its target_modules / this model: {extra[:4]}")
+    return Adapter(rank=r, layers=layers, target_modules=tuple(tm), digest=_adapter_digest(path), path=str(path))

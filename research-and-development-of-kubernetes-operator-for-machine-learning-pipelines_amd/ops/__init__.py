@@ -125,14 +125,41 @@ def rope_cache(qkv, positions, cos_sin, slots, k_cache, v_cache, n_q_heads: int,
     return q_out
 
 
-def silu_mul(x: torch.Tensor, out: torch.Tensor | None = None):
+def silu_mul(x: torch.Tensor, out: torch.Tensor | None = None, interleaved: bool = False):
+    """SiLU(gate) * up of [gate | up] columns, or (``interleaved``) of the 16-interleaved
+    columns an epilogue-free GEMM over ``interleave_gate_up`` weights produces."""
     if not x.is_cuda:
-        return ref.silu_mul(x)
+        return ref.silu_mul(deinterleave_cols(x) if interleaved else x)
     _need_gpu()
     I = x.shape[-1] // 2
     out = torch.empty(*x.shape[:-1], I, dtype=x.dtype, device=x.device) if out is None else out
-    torch.ops.mlop.silu_mul(out, x)
+    torch.ops.mlop.silu_mul(out, x, int(interleaved))
     return out
+
+
+def lora_shrink(x: torch.Tensor, A: torch.Tensor, tok_slot: torch.Tensor, slot_rank: torch.Tensor,
+                groups: int | None = None, out: torch.Tensor | None = None):
+    """Multi-LoRA shrink: tmp[t] = A[tok_slot[t]] . x[t], fp32 [T, G R] (zeros for slot -1).
+    x [T, K] bf16, A [S, G R, K] bf16, tok_slot [T] / slot_rank [S] int32.  ``groups`` = G lets
+    the kernel skip the rank tiles above a slot's rank (they are zero either way)."""
+    if not x.is_cuda:
+        return ref.lora_shrink(x, A, tok_slot, slot_rank)
+    _need_gpu()
+    tmp = torch.empty(x.shape[0], A.shape[1], dtype=torch.float32, device=x.device) if out is None else out
+    torch.ops.mlop.lora_shrink(tmp, x, A, tok_slot, slot_rank, A.shape[1] // groups if groups else 16)
+    return tmp
+
+
+def lora_expand_add(y: torch.Tensor, tmp: torch.Tensor, B: torch.Tensor, tile_group: torch.Tensor,
+                    tok_slot: torch.Tensor, slot_rank: torch.Tensor):
+    """Multi-LoRA expand, in place: y[t, n] += sum_r tmp[t, g(n) R + r] . B[tok_slot[t], n, r] with
+    g(n) = tile_group[n // 16]; B [S, N, R] bf16 carries the scaling.  Rows with slot -1 are
+    not written."""
+    if not y.is_cuda:
+        return ref.lora_expand_add(y, tmp, B, tile_group, tok_slot, slot_rank)
+    _need_gpu()
+    torch.ops.mlop.lora_expand_add(y, tmp, B, tile_group, tok_slot, slot_rank)
+    return y
 
 
 def embedding(ids: torch.Tensor, table: torch.Tensor, vocab_start: int = 0,

@@ -87,6 +87,47 @@ void silu_mul(Tensor out, Tensor x, int64_t interleaved) {
                         cur_stream());
 }
 
+// multi-LoRA (lora.hip): tmp[t] = A[tok_slot[t]] . x[t]
+// (R = rows per A block, for the rank skip; 16 = never skip) and
+// y[t, n] += sum_r tmp[t, g(n) R + r] . B[tok_slot[t], n, r] in place
+void lora_shrink(Tensor tmp, Tensor x, Tensor A, Tensor tok_slot, Tensor slot_rank, int64_t R) {
+  check_bf16(A, "A"); check_i32(tok_slot, "tok_slot"); check_i32(slot_rank, "slot_rank");
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 && x.dim() == 2 && x.stride(1) == 1 &&
+              x.stride(0) % 8 == 0, "x must be bf16 [T, K] with unit inner stride and 16-byte rows");
+  TORCH_CHECK(tmp.is_cuda() && tmp.scalar_type() == at::kFloat && tmp.is_contiguous() && tmp.dim() == 2,
+              "tmp must be contiguous fp32 [T, G R]");
+  TORCH_CHECK(A.dim() == 3, "A must be [S, G R, K]");
+  const int64_t T = x.size(0), K = x.size(1), S = A.size(0), GR = A.size(1);
+  TORCH_CHECK(K % 128 == 0 && A.size(2) == K, "lora_shrink: K must be a multiple of 128 and match A");
+  TORCH_CHECK(GR % 16 == 0 && tmp.size(0) == T && tmp.size(1) == GR, "lora_shrink: tmp shape");
+  TORCH_CHECK(R >= 16 && R % 16 == 0 && GR % R == 0, "lora_shrink: R must be a multiple of 16 dividing G R");
+  TORCH_CHECK(tok_slot.numel() == T && slot_rank.numel() == S, "lora_shrink: tok_slot [T], slot_rank [S]");
+  c10::DeviceGuard g(x.device());
+  mlop::launch_lora_shrink(x.data_ptr(), (int)x.stride(0), A.data_ptr(), tmp.data_ptr<float>(),
+                           tok_slot.data_ptr<int>(), slot_rank.data_ptr<int>(), (int)T, (int)K, (int)GR,
+                           (int)R, (int)S, cur_stream());
+}
+
+void lora_expand_add(Tensor y, Tensor tmp, Tensor B, Tensor tile_group, Tensor tok_slot, Tensor slot_rank) {
+  check_bf16(B, "B"); check_i32(tok_slot, "tok_slot"); check_i32(slot_rank, "slot_rank");
+  TORCH_CHECK(y.is_cuda() && y.scalar_type() == at::kBFloat16 && y.dim() == 2 && y.stride(1) == 1 &&
+              y.stride(0) % 8 == 0, "y must be bf16 [T, N] with unit inner stride and 16-byte rows");
+  TORCH_CHECK(tmp.is_cuda() && tmp.scalar_type() == at::kFloat && tmp.is_contiguous() && tmp.dim() == 2,
+              "tmp must be contiguous fp32 [T, G R]");
+  TORCH_CHECK(tile_group.is_cuda() && tile_group.scalar_type() == at::kByte && tile_group.is_contiguous(),
+              "tile_group must be uint8");
+  TORCH_CHECK(B.dim() == 3, "B must be [S, N, R]");
+  const int64_t T = y.size(0), N = y.size(1), S = B.size(0), R = B.size(2), GR = tmp.size(1);
+  TORCH_CHECK(N % 16 == 0 && B.size(1) == N && tile_group.numel() == N / 16, "lora_expand_add: N, tile_group");
+  TORCH_CHECK(R % 16 == 0 && R > 0 && GR % R == 0 && GR / R <= 255 && tmp.size(0) == T,
+              "lora_expand_add: tmp must be [T, G R] with R = B.size(2) a multiple of 16");
+  TORCH_CHECK(tok_slot.numel() == T && slot_rank.numel() == S, "lora_expand_add: tok_slot [T], slot_rank [S]");
+  c10::DeviceGuard g(y.device());
+  mlop::launch_lora_expand_add(y.data_ptr(), (int)y.stride(0), tmp.data_ptr<float>(), B.data_ptr(),
+                               tile_group.data_ptr<uint8_t>(), tok_slot.data_ptr<int>(),
+                               slot_rank.data_ptr<int>(), (int)T, (int)N, (int)GR, (int)R, (int)S, cur_stream());
+}
+
 // fault injection: a device-side delay of `us` microseconds on the current stream
 void device_delay(int64_t us) {
   int dev = 0, khz = 0;
@@ -1001,6 +1042,9 @@ TORCH_LIBRARY(mlop, m) {
   m.def("rope_cache(Tensor(a!) q_out, Tensor(b!) k_cache, Tensor(c!) v_cache, Tensor qkv, "
         "Tensor pos, Tensor cos_sin, Tensor slots) -> ()");
   m.def("silu_mul(Tensor(a!) out, Tensor x, int interleaved=0) -> ()");
+  m.def("lora_shrink(Tensor(a!) tmp, Tensor x, Tensor A, Tensor tok_slot, Tensor slot_rank, int R=16) -> ()");
+  m.def("lora_expand_add(Tensor(a!) y, Tensor tmp, Tensor B, Tensor tile_group, Tensor tok_slot, "
+        "Tensor slot_rank) -> ()");
   m.def("embedding(Tensor(a!) out, Tensor table, Tensor ids, int vocab_start) -> ()");
   m.def("gemm_ws(Tensor(a!) out, Tensor a, Tensor w, int epi, bool rs, float eps) -> bool");
   m.def("flash_prefill(Tensor(a!) out, Tensor q, Tensor k_cache, Tensor v_cache, Tensor block_tables, "
@@ -1018,6 +1062,8 @@ TORCH_LIBRARY_IMPL(mlop, CUDA, m) {
   m.impl("rope_cache", &rope_cache);
   m.impl("silu_mul", &silu_mul);
   m.impl("embedding", &embedding);
+  m.impl("lora_shrink", &lora_shrink);
+  m.impl("lora_expand_add", &lora_expand_add);
   m.impl("paged_attention", &paged_attention);
   m.impl("flash_prefill", &flash_prefill);
   m.impl("gemm", &gemm);

@@ -19,6 +19,12 @@ void launch_rope_cache(void* q_out, void* k_cache, void* v_cache, const void* qk
                        int qkv_stride, int BS, hipStream_t st);
 void launch_silu_mul(void* out, const void* x, int M, int I, int interleaved, hipStream_t st);
 void launch_device_delay(long long ticks, hipStream_t st);
+// lora.hip: per-token low-rank update (multi-LoRA)
+void launch_lora_shrink(const void* x, int ldx, const void* A, float* tmp, const int* tok_slot,
+                        const int* slot_rank, int T, int K, int GR, int R, int S, hipStream_t st);
+void launch_lora_expand_add(void* y, int ldy, const float* tmp, const void* B, const uint8_t* tile_group,
+                            const int* tok_slot, const int* slot_rank, int T, int N, int GR, int R, int S,
+                            hipStream_t st);
 void launch_embedding(void* out, const void* table, const long* ids, int T, int H, long vocab_start,
                       long vocab_end, hipStream_t st);
 void launch_paged_attention(void* out, float* part_o, float* part_ml, const void* q,

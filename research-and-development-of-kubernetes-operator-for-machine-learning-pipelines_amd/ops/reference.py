@@ -168,3 +168,32 @@ def moe_combine(y, inv, topw):
         if ok.any():
             out[ok] += topw[ok, j, None].float() * y[inv[ok, j]].float()
     return out.to(y.dtype)
+
+
+# ----------------------------------------------------------------- LoRA --
+
+def lora_shrink(x, A, tok_slot, slot_rank=None):
+    """tmp[t] = A[tok_slot[t]] . x[t] in fp32 ([T, G R]); rows with slot -1 are zero."""
+    T = x.shape[0]
+    tmp = torch.zeros(T, A.shape[1], dtype=torch.float32, device=x.device)
+    ts = tok_slot.long()
+    for s in torch.unique(ts[ts >= 0]).tolist():
+        rows = ts == s
+        tmp[rows] = x[rows].float() @ A[s].float().t()
+    return tmp
+
+
+def lora_expand_add(y, tmp, B, tile_group, tok_slot, slot_rank=None):
+    """In place: y[t, n] += sum_r tmp[t, g(n) R + r] . B[tok_slot[t], n, r] (fp32 sum, one rounding to
+    y's dtype); g(n) = tile_group[n // 16].  Rows with slot -1 are not written."""
+    R = B.shape[2]
+    ts = tok_slot.long()
+    col_g = tile_group.long().repeat_interleave(16)
+    for s in torch.unique(ts[ts >= 0]).tolist():
+        rows = torch.nonzero(ts == s, as_tuple=True)[0]
+        acc = y[rows].float()
+        for g in torch.unique(col_g).tolist():
+            cols = torch.nonzero(col_g == g, as_tuple=True)[0]
+            acc[:, cols] += tmp[rows, g * R:(g + 1) * R] @ B[s][cols].float().t()
+        y[rows] = acc.to(y.dtype)
+    return y

@@ -176,13 +176,22 @@ class LLMBackend:
     async def generate(self, prompt_ids, params: SamplingParams) -> dict:
         return await self.submit(prompt_ids, params).future
 
+    def check_params(self, params: SamplingParams) -> None:
+        """ValueError (HTTP 400) for what this predictor cannot serve: an adapter it has not loaded."""
+        if params.adapter is not None and params.adapter not in getattr(self.engine, "_adapters", {}):
+            raise ValueError(f"unknown adapter {params.adapter!r}")
+
     def metadata(self) -> dict:
         cfg = self.engine.model.cfg
-        return {"name": self.name, "platform": "mlopamd-llm-rocm", "architecture": cfg.name,
-                "inputs": [{"name": "text_input", "datatype": "BYTES", "shape": [-1]},
-                           {"name": "input_ids", "datatype": "INT64", "shape": [-1]}],
-                "outputs": [{"name": "text_output", "datatype": "BYTES", "shape": [-1]},
-                            {"name": "output_ids", "datatype": "INT64", "shape": [-1]}]}
+        md = {"name": self.name, "platform": "mlopamd-llm-rocm", "architecture": cfg.name,
+              "inputs": [{"name": "text_input", "datatype": "BYTES", "shape": [-1]},
+                         {"name": "input_ids", "datatype": "INT64", "shape": [-1]}],
+              "outputs": [{"name": "text_output", "datatype": "BYTES", "shape": [-1]},
+                          {"name": "output_ids", "datatype": "INT64", "shape": [-1]}]}
+        ads = self.engine.adapters() if getattr(self.engine, "lora", None) is not None else []
+        if ads:  # only when some are configured: the response is unchanged otherwise
+            md["adapters"] = [{"name": a["name"], "rank": a["rank"]} for a in ads]
+        return md
 
 
 def _set_res(fut, res):

@@ -181,6 +181,8 @@ class Sequence:
     n_rel: int = 0                              # leading pages released below the sliding window (null page 0)
     pen_slot: int = -1                          # row of the penalty count table held while admitted
     logprobs: list = field(default_factory=list)  # per output token (logprob, [(id, logprob), ...]) when asked for
+    slot: int = -1                              # LoRA adapter slot (-1: base model); kept across preemption
+    prefix_seed: bytes = b""                    # seed of the prefix hash chain: the adapter's identity
 
     @property
     def length(self) -> int:
@@ -226,6 +228,10 @@ class EngineConfig:
     # sliding-window models: give back the KV pages that fell wholly below a sequence's window
     # (False: keep them until the sequence ends; the A/B and debugging switch)
     swa_release: bool = True
+    # multi-LoRA: adapter slots held in HBM beside the base model (0 = feature off: nothing is
+    # allocated or captured) and the largest adapter rank a slot takes (<= 64)
+    max_adapters: int = 0
+    max_lora_rank: int = 64
 
 
 @dataclass
@@ -309,6 +315,18 @@ class Engine:
         self.device = model.device
         mc = model.cfg
         self.max_model_len = min(cfg.max_model_len, mc.max_position)
+        # multi-LoRA: the slot-major adapter stacks, allocated before the KV pool is sized from
+        # what is left (raises for Mixtral / TP > 1 / EP)
+        self.lora = None
+        self._adapters: dict[str, dict] = {}
+        if cfg.max_adapters > 0:
+            from ..models.lora import LoraStacks
+
+            self.lora = LoraStacks(model, cfg.max_adapters, cfg.max_lora_rank)
+        self._free_slots = list(range(max(0, cfg.max_adapters) - 1, -1, -1))
+        self._slot_refs = np.zeros(max(0, cfg.max_adapters), np.int64)  # live sequences per slot
+        self.graphs_lora: dict[int, tuple] = {}
+        self._step_lora = False  # the step being launched has at least one adapter row
         nb = cfg.num_kv_blocks or self._auto_blocks()
         tp = model.ps.tp
         self.step_sync = StepSync(tp, model.ps.tp_cpu) if tp.size > 1 else None
@@ -362,6 +380,7 @@ class Engine:
         self.r_pres = np.zeros(R, np.float32)
         self.r_want = np.full(R, -1, np.int32)
         self.r_sampler = np.zeros(R, bool)
+        self.r_slot = np.full(R, -1, np.int32)  # the row's LoRA adapter slot (-1: base model)
         self.pen_table = None  # int32 [penalty_slots, vocab]: allocated by the first request that needs it
         self.free_pen_slots = list(range(max(0, cfg.penalty_slots) - 1, -1, -1))
         self._last_lp = None   # the last _sample's (logprobs, ids) device tensors, or None
@@ -400,6 +419,13 @@ class Engine:
         self._toks_flip = 0
         self._src_h = torch.zeros(R, dtype=torch.int64, pin_memory=cuda)
         self._src_d = torch.zeros(R, dtype=torch.int64, device=self.device)
+        if self.lora is not None:
+            # per-token adapter slot of a step, beside the packed metadata (whose layout and upload
+            # stay as they are): pinned host side, rewritten only after _wait_meta like the metadata
+            self._ts_h = torch.full((nmax,), -1, dtype=torch.int32, pin_memory=cuda)
+            self._ts_hn = self._ts_h.numpy()
+            self._ts_d = torch.full((nmax,), -1, dtype=torch.int32, device=self.device)
+            self.stats["lora_bytes"] = self.lora.nbytes()
         if self.ep_sync is not None and self.device.type == "cuda":
             self._setup_ep_exchange()
         self.stats["kv_alloc_ms"] = kv_alloc_ms
@@ -478,6 +504,8 @@ class Engine:
         params = (params or SamplingParams()).validate()
         if params.penalised and self.cfg.penalty_slots <= 0:
             raise ValueError("this engine serves no penalised requests (penalty_slots = 0)")
+        if params.adapter is not None and params.adapter not in self._adapters:
+            raise ValueError(f"unknown adapter {params.adapter!r} (loaded: {sorted(self._adapters)})")
 
     def add_request(self, prompt, params: SamplingParams | None = None, seq_id: int | None = None) -> Sequence:
         params = params or SamplingParams()
@@ -485,6 +513,10 @@ class Engine:
         self.check_request(prompt, params)
         sid = next(self._ids) if seq_id is None else seq_id
         seq = Sequence(sid, prompt, params)
+        if params.adapter is not None:
+            ad = self._adapters[params.adapter]
+            seq.slot, seq.prefix_seed = ad["slot"], ad["seed"]
+            self._slot_refs[seq.slot] += 1
         self.seqs[sid] = seq
         self.waiting.append(seq)
         return seq
@@ -559,6 +591,7 @@ class Engine:
             seq.pen_slot = -1
         if seq.row >= 0:
             self.r_pen_slot[seq.row], self.r_want[seq.row] = -1, -1
+            self.r_slot[seq.row] = -1
             self.r_nblk[seq.row] = 0
             self.r_nrel[seq.row] = 0
             self.r_epoch[seq.row] += 1  # an in-flight step's result for this row is stale
@@ -578,6 +611,7 @@ class Engine:
         prompt (mask) and the output so far (counts: re-admission after preemption), on the
         engine's stream, so ahead of the first step that draws for it."""
         r, p = seq.row, seq.params
+        self.r_slot[r] = seq.slot
         self.r_sampler[r] = (not p.greedy) or p.extended
         self.r_want[r] = -1 if p.logprobs is None else p.logprobs
         self.r_pen_slot[r] = -1
@@ -616,6 +650,9 @@ class Engine:
         seq.finish_reason = reason
         seq.finish_time = time.perf_counter()
         self._release(seq)
+        if seq.slot >= 0:  # the adapter may be unloaded once no live sequence names it
+            self._slot_refs[seq.slot] -= 1
+            seq.slot = -1
 
     def _preempt(self, seq: Sequence):
         self.stats["preemptions"] += 1
@@ -763,7 +800,7 @@ class Engine:
         if nfull <= 0:
             return
         if len(seq.hashes) < nfull:
-            prev = seq.hashes[-1] if seq.hashes else b""
+            prev = seq.hashes[-1] if seq.hashes else seq.prefix_seed
             seq.hashes += prefix_hashes(seq.tokens(0, nfull * BLOCK_SIZE), nfull, len(seq.hashes), prev)
         m = 0
         for h in seq.hashes[:nfull]:
@@ -785,7 +822,7 @@ class Engine:
         if full <= seq.n_reg:
             return
         if len(seq.hashes) < full:
-            prev = seq.hashes[-1] if seq.hashes else b""
+            prev = seq.hashes[-1] if seq.hashes else seq.prefix_seed
             seq.hashes += prefix_hashes(seq.tokens(0, full * BLOCK_SIZE), full, len(seq.hashes), prev)
         for i in range(max(seq.n_reg, seq.n_rel), full):  # (not the null entries of released pages)
             self.alloc.register(seq.blocks[i], seq.hashes[i])
@@ -832,6 +869,7 @@ class Engine:
         toks = [s.tokens(s.num_cached, c) for s, c in zip(batch, ctx)]
         done = [c == s.length for s, c in zip(batch, ctx)]
         T, nt, nl = self.meta.fill(rows, chunks, ctx, toks, want_logits=done)
+        self._fill_tok_slot(T, (), batch, chunks)
         part, nparts = plan_partitions(nt, self.model.n_kv, self.meta.span(max(ctx)))
         done_params = [s.params for s, d in zip(batch, done) if d]
         logits = self._launch(KIND_EAGER, T, nt, nl, part, nparts, 0,
@@ -870,6 +908,7 @@ class Engine:
         done = [c == s.length for s, c in zip(batch, p_ctx)]
         T, nt, nl = self.meta.fill_mixed(rows, ctx_d.astype(np.int32), self.r_last[rows],
                                          p_rows, chunks, p_ctx, p_toks, want_logits=done)
+        self._fill_tok_slot(T, rows, batch, chunks)
         part, nparts = plan_partitions(nt, self.model.n_kv, self.meta.span(max(int(ctx_d.max()), max(p_ctx))))
         t1 = time.perf_counter()
         done_seqs = [s for s, d in zip(batch, done) if d]
@@ -976,6 +1015,7 @@ class Engine:
             p_toks = [s.tokens(s.num_cached, c) for s, c in zip(batch, p_ctx)]
             done = [c == s.length for s, c in zip(batch, p_ctx)]
             T, nt, nl = self.meta.fill_mixed(rows, ctx_d, last, p_rows, chunks, p_ctx, p_toks, want_logits=done)
+            self._fill_tok_slot(T, rows, batch, chunks)
             part, nparts = plan_partitions(nt, self.model.n_kv, self.meta.span(max(int(ctx_d.max()), max(p_ctx))))
             done_seqs = [s for s, d in zip(batch, done) if d]
             if greedy and not any(self.r_sampler[s.row] for s in done_seqs):
@@ -988,7 +1028,9 @@ class Engine:
             done_seqs = []
             params = dparams
             bucket = next((b for b in self.buckets if b >= B), None)
-            if bucket is not None and self.graphs.get(bucket) is not None:
+            has_graph = bucket is not None and self.graphs.get(bucket) is not None
+            self._fill_tok_slot(bucket if has_graph else B, rows)
+            if has_graph:
                 self.meta.fill_decode(rows, ctx_d, last, pad_to=bucket)
                 self._repad = (rows, ctx_d, last, int(ctx_d.max()))  # EP: the group may re-pad it
                 launch = (KIND_GRAPH, bucket, bucket, bucket, 0, 0, bucket)
@@ -1218,6 +1260,7 @@ class Engine:
         g = self.graphs.get(bucket) if bucket is not None else None
         params = self._params_of_running()
         greedy = getattr(params, "all_greedy", False)
+        self._fill_tok_slot(bucket if g is not None else B, rows)
         if g is not None:
             self.meta.fill_decode(rows, ctx, last, pad_to=bucket)
             self._repad = (rows, ctx, last, int(ctx.max()))
@@ -1242,6 +1285,73 @@ class Engine:
         self.stats["decode_device_us"] += int(1e6 * (t2 - t1))
         self.stats["decode_host_post_us"] += int(1e6 * (t3 - t2))
         return outs
+
+    def _fill_tok_slot(self, T: int, d_rows, batch=(), chunks=()) -> None:
+        """The step's adapter slot per token, in the metadata's token order: the decode rows, then
+        each prompt chunk; graph padding rows get -1.  Leaves ``_step_lora`` = some row of the
+        step uses an adapter (False: the step takes the adapter-free path, decode graphs included)."""
+        self._step_lora = False
+        if self.lora is None or not self._slot_refs.any():
+            return
+        ts = self._ts_hn
+        t = len(d_rows)
+        if t:
+            ts[:t] = self.r_slot[d_rows]
+        for s, n in zip(batch, chunks):
+            ts[t:t + n] = s.slot
+            t += n
+        ts[t:T] = -1
+        self._step_lora = bool((ts[:T] >= 0).any())
+
+    # --------------------------------------------------------- adapters --
+    def load_adapter(self, name: str, path) -> None:
+        """Load the PEFT-format LoRA adapter in ``path`` into a free slot under ``name``; requests
+        then select it with ``SamplingParams(adapter=name)``."""
+        if self.lora is None:
+            raise ValueError("this engine serves no adapters (EngineConfig.max_adapters = 0)")
+        from ..models.loader import load_adapter
+
+        self.add_adapter(name, load_adapter(path, self.model.cfg, self.cfg.max_lora_rank))
+
+    def add_adapter(self, name: str, ad) -> None:
+        """Install a ``models.lora.Adapter`` (already in our layout) under ``name``.  The copy into
+        the slot runs on the engine's stream, behind every launched step."""
+        if self.lora is None:
+            raise ValueError("this engine serves no adapters (EngineConfig.max_adapters = 0)")
+        if not isinstance(name, str) or not name:
+            raise ValueError("adapter name must be a non-empty string")
+        if name in self._adapters:
+            raise ValueError(f"adapter {name!r} is already loaded (unload it first)")
+        if not self._free_slots:
+            raise ValueError(f"all {self.cfg.max_adapters} adapter slots are in use")
+        slot = self._free_slots.pop()
+        try:
+            self.lora.load(slot, ad)
+        except Exception:
+            self.lora.clear(slot)
+            self._free_slots.append(slot)
+            raise
+        import hashlib
+
+        # prefix-cache identity: name + content, never the slot (a slot is reused)
+        seed = hashlib.blake2b(b"lora\0" + name.encode() + b"\0" + ad.digest, digest_size=16).digest()
+        self._adapters[name] = {"slot": slot, "seed": seed, "rank": ad.rank, "path": ad.path,
+                                "target_modules": list(ad.target_modules)}
+
+    def unload_adapter(self, name: str) -> None:
+        """Free an adapter's slot; refused while a live sequence references it."""
+        ad = self._adapters.get(name)
+        if ad is None:
+            raise ValueError(f"unknown adapter {name!r}")
+        if self._slot_refs[ad["slot"]] > 0:
+            raise RuntimeError(f"adapter {name!r} is in use by {int(self._slot_refs[ad['slot']])} live sequence(s)")
+        self.lora.clear(ad["slot"])
+        self._free_slots.append(ad["slot"])
+        del self._adapters[name]
+
+    def adapters(self) -> list:
+        """The loaded adapters: [{name, slot, rank, target_modules, path}]."""
+        return [{"name": n, **{k: v for k, v in a.items() if k != "seed"}} for n, a in self._adapters.items()]
 
     def _deliver_lp(self, seqs, lp, want) -> dict | None:
         """A step's log-probabilities onto the sequences that asked (``seqs`` aligned with the
@@ -1322,6 +1432,8 @@ class Engine:
         if self.ep_sync is not None:
             kind, T, nt, nl, part, nparts, bucket = self._ep_agree(kind, T, nt, nl, part, nparts, bucket)
         self.meta.upload(T, nl, self.rows_hi)
+        if self._step_lora:  # ahead of _meta_ev: the same event guards the pinned host side
+            self._ts_d[:T].copy_(self._ts_h[:T], non_blocking=True)
         g = self._ids_gather
         if g is not None:
             # async: decode rows' input ids = the previous (in-flight) step's sampled tokens,
@@ -1365,12 +1477,20 @@ class Engine:
     def _execute(self, kind, T, nt, nl, part, nparts, bucket, npt=0, greedy=0):
         if self._inject_device_us:  # fault injection: this step is slower on the device only
             torch.ops.mlop.device_delay(self._inject_device_us)
+        lora = self._step_lora
+        if lora:
+            self.stats["lora_steps"] += 1
         if kind == KIND_GRAPH:
-            graph, logits_buf = self.graphs[bucket]
+            graph, logits_buf = (self.graphs_lora if lora else self.graphs)[bucket]
             graph.replay()
+            if lora:
+                self.stats["lora_graph_steps"] += 1
             return self._gather(logits_buf, greedy)
         meta = self.meta.meta(T, nt, nl, part, nparts, npt)
-        hidden = self.model.forward(self.meta.ids_d[:T], meta, self.kv)
+        if lora:
+            hidden = self.model.forward(self.meta.ids_d[:T], meta, self.kv, lora=self.lora.step(self._ts_d[:T]))
+        else:
+            hidden = self.model.forward(self.meta.ids_d[:T], meta, self.kv)
         if nl == 0:
             return None
         return self._gather(self.model.logits_local(hidden[meta.logits_idx]), greedy)
@@ -1481,6 +1601,18 @@ class Engine:
                 with torch.cuda.graph(g, pool=self.graph_pool, stream=stream):
                     logits = m.logits_local(m.forward(ids, meta, self.kv))
                 self.graphs[b] = (g, logits)
+                if self.lora is not None:
+                    # second family: the LoRA forward of the same bucket, replayed by decode steps
+                    # with an adapter row.  It reads tok_slot and the slot stacks through fixed
+                    # pointers; captured with every row on the base model (-1)
+                    self._ts_d[:b].fill_(-1)
+                    step = self.lora.step(self._ts_d[:b])
+                    m.logits_local(m.forward(ids, meta, self.kv, lora=step))
+                    stream.synchronize()
+                    g = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(g, pool=self.graph_pool, stream=stream):
+                        logits = m.logits_local(m.forward(ids, meta, self.kv, lora=step))
+                    self.graphs_lora[b] = (g, logits)
         torch.cuda.current_stream(self.device).wait_stream(stream)
         torch.cuda.synchronize(self.device)
         self.stats["graph_capture_ms"] = int(1e3 * (time.perf_counter() - t0))

@@ -111,6 +111,8 @@ def check_ep_request(params) -> None:
     if params is not None and params.logprobs is not None:
         raise ValueError("logprobs are not supported by an expert-parallel (--ep) predictor: its control "
                          "plane returns token ids only")
+    if params is not None and getattr(params, "adapter", None) is not None:
+        raise ValueError("LoRA adapters are not supported by an expert-parallel (--ep) predictor")
 
 
 class EPGroupLoop:

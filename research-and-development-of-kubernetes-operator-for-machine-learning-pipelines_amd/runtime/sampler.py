@@ -41,6 +41,7 @@ class SamplingParams:
     presence_penalty: float = 0.0     # subtracted once from every id generated so far
     frequency_penalty: float = 0.0    # subtracted per occurrence in the output so far
     logprobs: int | None = None       # None: off; N: the token's logprob + the top N alternatives
+    adapter: str | None = None        # name of a loaded LoRA adapter (Engine.load_adapter); None: the base model
 
     @property
     def greedy(self) -> bool:
@@ -88,6 +89,8 @@ class SamplingParams:
         n = self.logprobs
         if n is not None and (isinstance(n, bool) or not isinstance(n, int) or not 0 <= n <= MAX_LOGPROBS):
             raise ValueError(f"logprobs must be None or an int in [0, {MAX_LOGPROBS}], got {n}")
+        if self.adapter is not None and (not isinstance(self.adapter, str) or not self.adapter):
+            raise ValueError(f"adapter must be None or a non-empty string, got {self.adapter!r}")
         return self
 
 

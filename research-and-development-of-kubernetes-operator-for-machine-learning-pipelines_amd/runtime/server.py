@@ -127,7 +127,10 @@ def _params(p: dict) -> SamplingParams:
     lp = p.get("logprobs")
     if lp is not None and (isinstance(lp, bool) or not isinstance(lp, int)):
         raise ValueError(f"logprobs must be an int, got {lp!r}")
-    return SamplingParams(max_tokens=int(p.get("max_tokens", 64)), temperature=float(p.get("temperature", 0.0)),
+    ad = p.get("adapter")
+    if ad is not None and not isinstance(ad, str):
+        raise ValueError(f"adapter must be a string, got {ad!r}")
+    return SamplingParams(adapter=ad, max_tokens=int(p.get("max_tokens", 64)), temperature=float(p.get("temperature", 0.0)),
                           top_k=int(p.get("top_k", 0)), top_p=float(p.get("top_p", 1.0)),
                           ignore_eos=bool(p.get("ignore_eos", False)),
                           stop_token_ids=list(p.get("stop_token_ids", [])),
@@ -354,6 +357,7 @@ def build_backend(runtime: str, model_uri: str | None, architecture: str | None,
     dtype = {"float32": torch.float32, "bfloat16": torch.bfloat16}[os.environ.get("MLOP_DTYPE", "bfloat16")]
     eng = build_engine(architecture or "llama3-8b", device=device, seed=seed, tp_state=tp_state,
                        model_uri=model_uri, dtype=dtype, **(engine_kwargs or {}))
+    load_env_adapters(eng)
     STARTUP["engine_built_s"] = _since_process_start()
     STARTUP["engine"] = {k: int(eng.stats.get(k, 0)) for k in ("model_build_ms", "kv_alloc_ms", "graph_capture_ms")}
     from .. import ops
@@ -365,6 +369,26 @@ def build_backend(runtime: str, model_uri: str | None, architecture: str | None,
         metrics.load_seconds.labels(**metrics.labels).set(time.perf_counter() - t0)
         metrics.ready.labels(**metrics.labels).set(1)
     return LLMBackend(eng, metrics, tokenizer=load_tokenizer(eng.checkpoint_dir), name=name).start()
+
+
+def load_env_adapters(eng) -> list:
+    """Load the LoRA adapters of ``MLOP_ADAPTERS`` (JSON ``[{"name": ..., "uri": ...}]``, set by the
+    operator from ``spec.adapters``) before the predictor reports ready.  URIs follow the model
+    URI rules (``models.loader.resolve_adapter_dir``); one that does not resolve fails start-up."""
+    raw = os.environ.get("MLOP_ADAPTERS")
+    if not raw:
+        return []
+    from ..models.loader import resolve_adapter_dir
+
+    specs = json.loads(raw)
+    if not isinstance(specs, list) or not all(isinstance(a, dict) and a.get("name") and a.get("uri") for a in specs):
+        raise ValueError("MLOP_ADAPTERS must be a JSON list of {\"name\": ..., \"uri\": ...}")
+    for a in specs:
+        d = resolve_adapter_dir(a["uri"])
+        if d is None:
+            raise FileNotFoundError(f"adapter {a['name']!r}: no adapter_config.json reachable at {a['uri']!r}")
+        eng.load_adapter(a["name"], d)
+    return [a["name"] for a in specs]
 
 
 def engine_kwargs_from_env() -> dict:
