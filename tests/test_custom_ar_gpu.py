@@ -192,7 +192,13 @@ def _worker(rank, world, port, out_dir, split):
 def test_custom_all_reduce_two_processes_one_gpu(world, split):
     """world = 8: the NR = 8 kernels (Llama-3-70B TP = 8) with 8 processes sharing the GPU.
     ``split``: the data parities in their own cached buffer (flags alone uncached) vs one
-    uncached buffer for both -- every kernel bit-exact either way."""
+    uncached buffer for both -- every kernel bit-exact either way.
+
+    world = 8 needs the 8 ranks' kernels resident together, so it has to run BEFORE any test that
+    opens the GPU in the pytest process itself: with that ninth context the ranks' hardware queues
+    are rotated and the bounded flag waits run out (measured: 7 s and passing alone, 115 s and
+    "a flag wait timed out" behind one in-process kernel test; profiles/attention_probes.md).  In
+    the suite's alphabetical order no such test file comes before this one: keep it that way."""
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     d = tempfile.mkdtemp()
