@@ -86,6 +86,9 @@ class CanaryPolicy:
                    gpu_guards=dict(base.gpu_guards if c.get("gpuGuards") is None else c["gpuGuards"]))
 
 
+KV_CACHE_DTYPES = ("bf16", "fp8")  # spec.kvCacheDtype (manifests/crd.yaml's enum)
+
+
 @dataclass(frozen=True)
 class ModelSpec:
     model_name: str
@@ -103,6 +106,8 @@ class ModelSpec:
     canary: CanaryPolicy = field(default_factory=CanaryPolicy)
     # LoRA adapters served beside the base model by the LLM runtime: ((name, uri), ...)
     adapters: tuple = ()
+    # KV cache element type of the LLM runtime: None / "bf16", or "fp8" (e4m3fn pages + row scales)
+    kv_cache_dtype: str | None = None
 
     @classmethod
     def from_spec(cls, spec: dict) -> "ModelSpec":
@@ -118,7 +123,8 @@ class ModelSpec:
                    kv_target_fraction=spec.get("kvTargetFraction"),
                    canary=CanaryPolicy.from_spec(spec),
                    adapters=tuple((a.get("name"), a.get("uri")) for a in (spec.get("adapters") or [])
-                                  if isinstance(a, dict)))
+                                  if isinstance(a, dict)),
+                   kv_cache_dtype=spec.get("kvCacheDtype"))
 
     def validate(self) -> list[str]:
         errs = []
@@ -137,6 +143,11 @@ class ModelSpec:
             if int(self.tensor_parallel or 1) > 1 or int(self.expert_parallel or 1) > 1:
                 errs.append("spec.adapters needs tensorParallel = 1 and expertParallel = 1 "
                             "(LoRA adapters are not sharded)")
+        if self.kv_cache_dtype is not None:
+            if self.kv_cache_dtype not in KV_CACHE_DTYPES:
+                errs.append(f"spec.kvCacheDtype must be one of {list(KV_CACHE_DTYPES)}, not {self.kv_cache_dtype!r}")
+            elif self.kv_cache_dtype == "fp8" and int(self.expert_parallel or 1) > 1:
+                errs.append("spec.kvCacheDtype fp8 needs expertParallel = 1 (no fp8 KV cache for MoE / EP engines)")
         return errs
 
 

@@ -46,12 +46,15 @@ def _valid_tp(cfg: ModelConfig, tp: int) -> bool:
 def plan(arch: str | ModelConfig, max_model_len: int = 4096, max_num_seqs: int = 256,
          hbm_gb: float = 288.0, gpus_per_node: int = 8, utilization: float = 0.90,
          reserve_gb: float = 8.0, requested_tp: int | None = None, requested_ep: int | None = None,
-         kv_target_fraction: float = 0.5, free_gpus: int | None = None) -> Placement:
+         kv_target_fraction: float = 0.5, free_gpus: int | None = None,
+         kv_cache_dtype: str | None = None) -> Placement:
     """``free_gpus``: GPUs the target node still has unallocated (reconciler.node_capacity);
     a placement needing more is returned with ``fits=False`` and the reason (the pod would
-    stay Pending), whatever its HBM arithmetic says."""
+    stay Pending), whatever its HBM arithmetic says.  ``kv_cache_dtype`` ("bf16" / "fp8"): the
+    engine's KV cache format; the KV target and capacity use its bytes per token, scale bytes
+    included (None: bf16)."""
     p = _plan(arch, max_model_len, max_num_seqs, hbm_gb, gpus_per_node, utilization, reserve_gb,
-              requested_tp, requested_ep, kv_target_fraction)
+              requested_tp, requested_ep, kv_target_fraction, kv_cache_dtype)
     if free_gpus is not None and p.gpus > free_gpus:
         p.fits = False
         p.reason = (f"needs {p.gpus} GPUs (TP={p.tensorParallel}), the node has {free_gpus} of "
@@ -60,11 +63,11 @@ def plan(arch: str | ModelConfig, max_model_len: int = 4096, max_num_seqs: int =
 
 
 def _plan(arch, max_model_len, max_num_seqs, hbm_gb, gpus_per_node, utilization, reserve_gb, requested_tp,
-          requested_ep, kv_target_fraction) -> Placement:
+          requested_ep, kv_target_fraction, kv_cache_dtype=None) -> Placement:
     cfg = arch if isinstance(arch, ModelConfig) else get_config(arch)
     usable = hbm_gb * utilization
     wbytes = cfg.weight_bytes()
-    kv_tok = cfg.kv_bytes_per_token()
+    kv_tok = cfg.kv_bytes_per_token(kv_cache_dtype=kv_cache_dtype or "bf16")
     kv_target = max_num_seqs * max_model_len * kv_tok * kv_target_fraction
 
     def evaluate(tp: int, ep: int) -> Placement:

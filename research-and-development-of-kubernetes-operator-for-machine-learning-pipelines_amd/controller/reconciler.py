@@ -205,7 +205,9 @@ class MlflowModelReconciler:
         free capacity: a deployed predictor keeps its placement while this key is unchanged."""
         return (f"{arch}|tp={spec.tensor_parallel or 0}|ep={spec.expert_parallel or 0}"
                 f"|len={spec.max_model_len or 4096}|seqs={spec.max_num_seqs or 256}"
-                f"|kvf={spec.kv_target_fraction or 0.5}|replicas={spec.replicas}")
+                f"|kvf={spec.kv_target_fraction or 0.5}|replicas={spec.replicas}"
+                # (appended only when set: CRs without the field keep the key their deployed predictors carry)
+                + (f"|kv={spec.kv_cache_dtype}" if spec.kv_cache_dtype else ""))
 
     async def desired_sd(self, body: dict, spec: ModelSpec, status: dict) -> dict | None:
         """The SeldonDeployment this CR wants now.  Placement is decided ONCE per version, like
@@ -257,7 +259,7 @@ class MlflowModelReconciler:
                              gpus_per_node=node.get("gpus", self.settings.gpus_per_node),
                              requested_tp=spec.tensor_parallel, requested_ep=spec.expert_parallel,
                              kv_target_fraction=spec.kv_target_fraction or 0.5,
-                             free_gpus=node.get("free_gpus"))
+                             free_gpus=node.get("free_gpus"), kv_cache_dtype=spec.kv_cache_dtype)
                     placement = {"tensorParallel": p.tensorParallel, "expertParallel": p.expertParallel,
                                  "gpus": p.gpus, "weightGBPerGPU": p.weightGBPerGPU,
                                  "kvTokenCapacity": p.kvTokenCapacity, "fits": p.fits, "placementKey": key}
@@ -282,6 +284,8 @@ class MlflowModelReconciler:
                 engine_args["max_model_len"] = spec.max_model_len
             if spec.max_num_seqs:
                 engine_args["max_num_seqs"] = spec.max_num_seqs
+            if spec.kv_cache_dtype and runtime == seldon.RUNTIME_LLM:
+                engine_args["kv_cache_dtype"] = spec.kv_cache_dtype  # -> MLOP_ENGINE_KV_CACHE_DTYPE
             preds.append(seldon.build_predictor(
                 v, uri, spec.minio_secret, traffic, runtime=runtime, replicas=spec.replicas, placement=placement,
                 image=self.settings.runtime_image, gpu_resource=self.settings.gpu_resource,

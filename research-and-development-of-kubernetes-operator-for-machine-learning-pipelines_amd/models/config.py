@@ -8,6 +8,15 @@ from __future__ import annotations
 
 from dataclasses import asdict, dataclass, field, replace
 
+# kv_cache_dtype -> (bytes per cached element, scale bytes per (token, kv head) row of K and of V)
+KV_CACHE_DTYPE_BYTES = {"bf16": (2, 0), "fp8": (1, 1)}
+
+
+def kv_dtype_bytes(name: str) -> tuple[int, int]:
+    if name not in KV_CACHE_DTYPE_BYTES:
+        raise ValueError(f"kv_cache_dtype must be one of {sorted(KV_CACHE_DTYPE_BYTES)}, not {name!r}")
+    return KV_CACHE_DTYPE_BYTES[name]
+
 
 @dataclass(frozen=True)
 class ModelConfig:
@@ -70,8 +79,13 @@ class ModelConfig:
     def weight_bytes(self, dtype_bytes: int = 2) -> int:
         return self.num_params() * dtype_bytes
 
-    def kv_bytes_per_token(self, dtype_bytes: int = 2) -> int:
-        return 2 * self.num_layers * self.kv_size * dtype_bytes
+    def kv_bytes_per_token(self, dtype_bytes: int = 2, kv_cache_dtype: str | None = None) -> int:
+        """KV cache bytes of one token over all layers.  ``kv_cache_dtype`` ("bf16" / "fp8"): the
+        engine's cache format, its per-row scale bytes included (it overrides ``dtype_bytes``)."""
+        scale_bytes = 0
+        if kv_cache_dtype is not None:
+            dtype_bytes, scale_bytes = kv_dtype_bytes(kv_cache_dtype)
+        return 2 * self.num_layers * (self.kv_size * dtype_bytes + self.num_kv_heads * scale_bytes)
 
     def flops_per_token(self) -> int:
         """Matmul FLOPs of one forward token (2 * active params, attention excluded)."""

@@ -172,7 +172,11 @@ class LlamaModel:
         M = ids.shape[0]
         # TP > 1: the decode (GEMV) form only, its residual adds riding in the all-reduces
         dmax = ops.decode_chain_max_m()  # the GEMV (<= 4 rows) / weight-streaming MFMA (<= 64) forms
-        chain = (tp.size == 1 or M <= dmax) and self._chain_ok(M)
+        # fp8 KV cache: the QKV epilogues that write the cache (fused RoPE, and the norm chain's
+        # row-scaled forms of it) are bf16-only, so the layer runs unfused - norm, plain QKV GEMM,
+        # kv_fp8.hip's RoPE + quantising writer - and every chain form is off
+        fp8 = getattr(kv, "fp8", False)
+        chain = not fp8 and (tp.size == 1 or M <= dmax) and self._chain_ok(M)
         ss = None  # norm chain: x is None and ss holds the residual's row partials
         if chain and M <= dmax:
             # decode form: the QKV GEMV takes the embedding rows' factors itself (ss unused)
@@ -180,13 +184,16 @@ class LlamaModel:
         else:
             x = ops.rmsnorm(h, self.layers[0]["in_norm"], eps)
         for i, L in enumerate(self.layers):
-            if ss is None:
+            if fp8:
+                q = ops.rope_cache(ops.gemm(x, L["qkv"]), meta.positions, self.cos_sin, meta.slots, kv.k[i], kv.v[i],
+                                   self.n_q, **kv.scales(i))
+            elif ss is None:
                 q = ops.qkv_rope_cache(x, L["qkv"], meta.positions, self.cos_sin, meta.slots, kv.k[i], kv.v[i],
                                        self.n_q)
             else:
                 q = ops.qkv_rope_cache_rs(residual, L["qkv"], meta.positions, self.cos_sin, meta.slots, kv.k[i],
                                           kv.v[i], self.n_q, ss, eps)
-            a = ops.paged_attention(q, kv.k[i], kv.v[i], meta)
+            a = ops.paged_attention(q, kv.k[i], kv.v[i], meta, **kv.scales(i))
             nxt = self.layers[i + 1]["in_norm"] if i + 1 < len(self.layers) else self.final_norm
             if chain and tp.size > 1:
                 x, ss = self._chain_layer_tp(i, a.view(a.shape[0], -1), residual, i + 1 == len(self.layers), eps, ss)
@@ -221,8 +228,9 @@ class LlamaModel:
         x = ops.rmsnorm(residual, self.layers[0]["in_norm"], eps)
         for i, (L, S) in enumerate(zip(self.layers, lora.layers)):
             qkv = proj(x, L, S, "qkv")
-            q = ops.rope_cache(qkv, meta.positions, self.cos_sin, meta.slots, kv.k[i], kv.v[i], self.n_q)
-            a = ops.paged_attention(q, kv.k[i], kv.v[i], meta)
+            q = ops.rope_cache(qkv, meta.positions, self.cos_sin, meta.slots, kv.k[i], kv.v[i], self.n_q,
+                               **kv.scales(i))
+            a = ops.paged_attention(q, kv.k[i], kv.v[i], meta, **kv.scales(i))
             o = proj(a.view(a.shape[0], -1), L, S, "o")
             x = ops.add_rmsnorm(o, residual, L["post_norm"], eps)
             act = ops.silu_mul(proj(x, L, S, "gate_up"), interleaved=True)

@@ -33,8 +33,13 @@ def _mlp(model, i, x):
 
 
 @torch.no_grad()
-def dense_logits(model, tokens) -> torch.Tensor:
-    """[T, V] fp32 logits of a single sequence (TP=1 models only)."""
+def dense_logits(model, tokens, kv_cache_dtype: str | None = None) -> torch.Tensor:
+    """[T, V] fp32 logits of a single sequence (TP=1 models only).  ``kv_cache_dtype="fp8"``: the
+    post-RoPE K and the V rows go through the fp8 KV cache's format per (token, kv head)
+    (``ops.reference.fp8_fake_quant``), the oracle of an engine with that cache; None / "bf16":
+    no quantisation."""
+    if kv_cache_dtype not in (None, "bf16", "fp8"):
+        raise ValueError(f"kv_cache_dtype {kv_cache_dtype!r}")
     cfg = model.cfg
     dev = model.embed.device
     T = len(tokens)
@@ -54,7 +59,11 @@ def dense_logits(model, tokens) -> torch.Tensor:
         k = qkv[:, model.n_q * D:(model.n_q + model.n_kv) * D].view(T, model.n_kv, D)
         v = qkv[:, (model.n_q + model.n_kv) * D:].view(T, model.n_kv, D)
         q = ref.rotate(q, cs[:, None, :half], cs[:, None, half:])
-        k = ref.rotate(k, cs[:, None, :half], cs[:, None, half:]).repeat_interleave(G, 1)
+        k = ref.rotate(k, cs[:, None, :half], cs[:, None, half:])
+        if kv_cache_dtype == "fp8":
+            # the cache quantises the rows as a cache of the model's dtype would hold them
+            k, v = ref.fp8_fake_quant(k.to(model.dtype)), ref.fp8_fake_quant(v.to(model.dtype))
+        k = k.repeat_interleave(G, 1)
         v = v.repeat_interleave(G, 1)
         s = torch.einsum("qhd,khd->hqk", q, k) / D ** 0.5
         s = s.masked_fill(mask[None], float("-inf"))

@@ -109,19 +109,35 @@ def add_rmsnorm(x: torch.Tensor, residual: torch.Tensor, w: torch.Tensor, eps: f
     return out
 
 
+def _fp8_scales(k_cache, k_scale, v_scale) -> bool:
+    """True for an fp8 (e4m3fn) KV cache, which must come with its scale-byte tensors."""
+    if k_cache.dtype != ref.FP8:
+        return False
+    if k_scale is None or v_scale is None:
+        raise ValueError("an fp8 KV cache needs its scale tensors (k_scale / v_scale)")
+    return True
+
+
 def rope_cache(qkv, positions, cos_sin, slots, k_cache, v_cache, n_q_heads: int,
-               q_out: torch.Tensor | None = None):
+               q_out: torch.Tensor | None = None, k_scale: torch.Tensor | None = None,
+               v_scale: torch.Tensor | None = None):
+    """RoPE + paged-cache write.  The cache's dtype picks the writer: bf16 pages, or e4m3fn pages
+    with their ``k_scale`` / ``v_scale`` bytes [NB, Hkv, 16] (kv_fp8.hip; ``ref.fp8_quantize_rows``)."""
     T = qkv.shape[0]
     D = k_cache.shape[3]
+    fp8 = _fp8_scales(k_cache, k_scale, v_scale)
     if not qkv.is_cuda:
-        q = ref.rope_cache(qkv, positions, cos_sin, slots, k_cache, v_cache, n_q_heads)
+        q = ref.rope_cache(qkv, positions, cos_sin, slots, k_cache, v_cache, n_q_heads, k_scale, v_scale)
         if q_out is not None:
             q_out.copy_(q)
             return q_out
         return q
     _need_gpu()
     q_out = torch.empty(T, n_q_heads, D, dtype=qkv.dtype, device=qkv.device) if q_out is None else q_out
-    torch.ops.mlop.rope_cache(q_out, k_cache, v_cache, qkv, positions, cos_sin, slots)
+    if fp8:
+        torch.ops.mlop.rope_cache_fp8(q_out, k_cache, v_cache, k_scale, v_scale, qkv, positions, cos_sin, slots)
+    else:
+        torch.ops.mlop.rope_cache(q_out, k_cache, v_cache, qkv, positions, cos_sin, slots)
     return q_out
 
 
@@ -182,16 +198,32 @@ def _no_sem(device):
     return t
 
 
-def paged_attention(q, k_cache, v_cache, meta, out: torch.Tensor | None = None):
+def paged_attention(q, k_cache, v_cache, meta, out: torch.Tensor | None = None,
+                    k_scale: torch.Tensor | None = None, v_scale: torch.Tensor | None = None):
     """Ragged paged attention; ``meta`` is a ``mlopamd.runtime.attn_meta.AttnMeta``.
     Decode / short rows run on the 16-q-row tiles (``tile_*``), prompt chunks on
-    the flash-prefill tiles (``ptile_*``); both write disjoint rows of ``out``."""
+    the flash-prefill tiles (``ptile_*``); both write disjoint rows of ``out``.
+    An e4m3fn cache (with its scale bytes) runs attention_fp8.hip's kernel on the 16-row
+    tiles only: no sliding window and no flash tiles (a missing kernel is an error)."""
+    fp8 = _fp8_scales(k_cache, k_scale, v_scale)
     if not q.is_cuda:
-        return ref.paged_attention(q, k_cache, v_cache, meta)
+        return ref.paged_attention(q, k_cache, v_cache, meta, k_scale, v_scale)
     _need_gpu()
     out = torch.empty_like(q) if out is None else out
     scale = 1.0 / math.sqrt(q.shape[-1])
     window = getattr(meta, "window", 0)  # sliding window (keys i - W < j <= i); 0 = none
+    if fp8:
+        pts = getattr(meta, "ptile_seq", None)
+        if window or (pts is not None and pts.numel()):
+            raise NotImplementedError("fp8 KV cache: no sliding-window and no flash-prefill kernel "
+                                      "(build the metadata with flash_min_q = 1 << 30)")
+        if meta.tile_seq.numel():
+            sem = getattr(meta, "part_sem", None)
+            torch.ops.mlop.paged_attention_fp8(out, meta.part_o, meta.part_ml, _no_sem(q.device) if sem is None else sem,
+                                               q, k_cache, v_cache, k_scale, v_scale, meta.block_tables,
+                                               meta.tile_seq, meta.tile_q0, meta.q_start, meta.q_len, meta.ctx_len,
+                                               scale, meta.part_tokens, meta.nparts)
+        return out
     if meta.tile_seq.numel():
         sem = getattr(meta, "part_sem", None)
         if sem is None:

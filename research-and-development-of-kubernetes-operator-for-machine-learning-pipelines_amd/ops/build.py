@@ -82,7 +82,8 @@ def _stale(obj: Path, src: Path, headers, cmd) -> tuple[bool, str]:
 # attention outputs.  -fno-slp-vectorize: no v_pk_mul_f32 / v_pk_add_f32 from adjacent f32 ops
 # (the O rescale): a packed f32 op beside MFMAs costs ~22-26 cycles more than two scalar ones
 # (MI355X_MICROARCH.md, per-instruction constants).
-FILE_FLAGS = {"attention": ["-fno-honor-nans", "-fno-slp-vectorize"]}
+_ATTN_FLAGS = ["-fno-honor-nans", "-fno-slp-vectorize"]
+FILE_FLAGS = {"attention": _ATTN_FLAGS, "attention_fp8": _ATTN_FLAGS}
 
 
 def _run(cmd):

@@ -459,6 +459,24 @@ static void launch_g(void* out, float* part_o, float* part_ml, const void* q, co
   }
 }
 
+// the split-KV combine as a launch of its own, for attention_fp8.hip: the partials are fp32
+// whatever the KV dtype, so the fp8 kernel ends in the same (unwindowed) reduce
+void launch_attn_reduce(void* out, const float* part_o, const float* part_ml, const int* tile_seq,
+                        const int* tile_q0, const int* q_start, const int* q_len, const int* ctx_len,
+                        int num_tiles, int Hq, int Hkv, int part_tokens, int nparts, hipStream_t st) {
+  auto red = attn_reduce_kernel<1, false>;
+  switch (Hq / Hkv) {
+    case 1: break;
+    case 2: red = attn_reduce_kernel<2, false>; break;
+    case 4: red = attn_reduce_kernel<4, false>; break;
+    case 8: red = attn_reduce_kernel<8, false>; break;
+    case 16: red = attn_reduce_kernel<16, false>; break;
+    default: return;
+  }
+  red<<<dim3(num_tiles, Hkv), 256, 0, st>>>((uint16_t*)out, part_o, part_ml, tile_seq, tile_q0, q_start, q_len,
+                                            ctx_len, Hq, Hkv, part_tokens, nparts, 0);
+}
+
 void launch_paged_attention(void* out, float* part_o, float* part_ml, const void* q,
                             const void* kc, const void* vc, const int* bt, int bt_stride,
                             const int* tile_seq, const int* tile_q0, const int* q_start,

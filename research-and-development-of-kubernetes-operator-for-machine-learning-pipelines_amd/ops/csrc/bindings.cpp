@@ -251,6 +251,90 @@ void paged_attention(Tensor out, Tensor part_o, Tensor part_ml, Tensor part_sem,
       (int)part_tokens, (int)nparts, (int)k_cache.size(0), sem, (int)window, cur_stream());
 }
 
+// ---- fp8 KV cache (kv_fp8.hip, attention_fp8.hip): e4m3fn pages + one scale byte per row
+void check_fp8_cache(const Tensor& c, const Tensor& sc, const char* name) {
+  TORCH_CHECK(c.is_cuda() && c.scalar_type() == at::kFloat8_e4m3fn && c.is_contiguous(), name,
+              " must be a contiguous float8_e4m3fn GPU tensor");
+  TORCH_CHECK(c.dim() == 4 && c.size(2) == 16 && c.size(3) == 128, name, " must be [NB, Hkv, 16, 128]");
+  TORCH_CHECK(sc.is_cuda() && sc.scalar_type() == at::kByte && sc.is_contiguous(), name,
+              " scales must be a contiguous uint8 GPU tensor");
+  TORCH_CHECK(sc.sizes() == at::IntArrayRef({c.size(0), c.size(1), 16}), name, " scales must be [NB, Hkv, 16]");
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(c.data_ptr()) & 15) == 0 &&
+                  (reinterpret_cast<uintptr_t>(sc.data_ptr()) & 15) == 0,
+              name, " and its scales must be 16-B aligned");
+}
+
+void rope_cache_fp8(Tensor q_out, Tensor k_cache, Tensor v_cache, Tensor k_scale, Tensor v_scale, Tensor qkv,
+                    Tensor pos, Tensor cos_sin, Tensor slots) {
+  check_bf16(q_out, "q_out");
+  check_fp8_cache(k_cache, k_scale, "k_cache"); check_fp8_cache(v_cache, v_scale, "v_cache");
+  check_i32(pos, "pos"); check_i32(slots, "slots");
+  TORCH_CHECK(qkv.is_cuda() && qkv.scalar_type() == at::kBFloat16 && qkv.stride(-1) == 1 && qkv.dim() == 2,
+              "qkv must be 2-d bf16 with unit inner stride");
+  TORCH_CHECK(cos_sin.is_cuda() && cos_sin.scalar_type() == at::kFloat && cos_sin.is_contiguous(), "cos_sin f32");
+  TORCH_CHECK(q_out.dim() == 3 && q_out.size(2) == 128, "q_out must be [T, Hq, 128]");
+  const int T = (int)q_out.size(0), Hq = (int)q_out.size(1);
+  const int Hkv = (int)k_cache.size(1);
+  TORCH_CHECK(v_cache.sizes() == k_cache.sizes(), "k and v caches differ in shape");
+  TORCH_CHECK(qkv.size(0) == T && qkv.size(-1) >= (Hq + 2 * Hkv) * 128 && qkv.stride(0) % 8 == 0 &&
+                  (reinterpret_cast<uintptr_t>(qkv.data_ptr()) & 15) == 0,
+              "qkv shape / alignment");
+  TORCH_CHECK(pos.numel() == T && slots.numel() == T, "pos/slots length");
+  TORCH_CHECK(cos_sin.dim() == 2 && cos_sin.size(1) == 128, "cos_sin must be [max_pos, 128]");
+  c10::DeviceGuard g(qkv.device());
+  mlop::launch_rope_cache_fp8(q_out.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), k_scale.data_ptr(),
+                              v_scale.data_ptr(), qkv.data_ptr(), pos.data_ptr<int>(),
+                              cos_sin.data_ptr<float>(), slots.data_ptr<int>(), T, Hq, Hkv,
+                              (int)qkv.stride(0), 16, cur_stream());
+}
+
+void paged_attention_fp8(Tensor out, Tensor part_o, Tensor part_ml, Tensor part_sem, Tensor q, Tensor k_cache,
+                         Tensor v_cache, Tensor k_scale, Tensor v_scale, Tensor block_tables, Tensor tile_seq,
+                         Tensor tile_q0, Tensor q_start, Tensor q_len, Tensor ctx_len, double scale,
+                         int64_t part_tokens, int64_t nparts) {
+  check_bf16(out, "out"); check_bf16(q, "q");
+  check_fp8_cache(k_cache, k_scale, "k_cache"); check_fp8_cache(v_cache, v_scale, "v_cache");
+  check_i32(block_tables, "block_tables"); check_i32(tile_seq, "tile_seq");
+  check_i32(tile_q0, "tile_q0"); check_i32(q_start, "q_start"); check_i32(q_len, "q_len");
+  check_i32(ctx_len, "ctx_len");
+  TORCH_CHECK(q.dim() == 3 && q.size(2) == 128, "q must be [T, Hq, 128]");
+  TORCH_CHECK(v_cache.sizes() == k_cache.sizes(), "k and v caches differ in shape");
+  const int Hq = (int)q.size(1), Hkv = (int)k_cache.size(1);
+  TORCH_CHECK(Hq % Hkv == 0, "Hq % Hkv");
+  const int G = Hq / Hkv;
+  TORCH_CHECK(G == 1 || G == 2 || G == 4 || G == 8 || G == 16, "GQA group must divide 16");
+  TORCH_CHECK(out.sizes() == q.sizes(), "out shape");
+  TORCH_CHECK(tile_seq.numel() == tile_q0.numel(), "tile arrays");
+  TORCH_CHECK(block_tables.dim() == 2 && block_tables.size(1) >= 1, "block_tables must be [rows, pages]");
+  TORCH_CHECK(q_start.numel() == q_len.numel() && q_len.numel() == ctx_len.numel() &&
+                  block_tables.size(0) >= q_len.numel(),
+              "per-sequence arrays");
+  TORCH_CHECK(part_tokens % 32 == 0 && part_tokens > 0 && nparts >= 1, "partition size");
+  const int num_tiles = (int)tile_seq.numel();
+  if (nparts > 1) {
+    TORCH_CHECK(part_o.scalar_type() == at::kFloat && part_ml.scalar_type() == at::kFloat, "partials f32");
+    TORCH_CHECK(part_o.numel() >= (int64_t)num_tiles * Hkv * nparts * 16 * 128 &&
+                    part_ml.numel() >= (int64_t)num_tiles * Hkv * nparts * 16 * 2,
+                "partial workspace too small");
+  }
+  // part_sem as paged_attention: zeroed tickets -> in-launch combine, empty -> reduce launch
+  int* sem = nullptr;
+  if (nparts > 1 && part_sem.numel() > 0 && num_tiles * Hkv <= attn_fused_pairs_cap()) {
+    check_i32(part_sem, "part_sem");
+    TORCH_CHECK(part_sem.numel() >= (int64_t)num_tiles * Hkv, "part_sem too small");
+    sem = part_sem.data_ptr<int>();
+  }
+  c10::DeviceGuard g(q.device());
+  const float scale_log2 = (float)(scale * 1.4426950408889634);
+  mlop::launch_paged_attention_fp8(
+      out.data_ptr(), nparts > 1 ? part_o.data_ptr<float>() : nullptr,
+      nparts > 1 ? part_ml.data_ptr<float>() : nullptr, q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
+      k_scale.data_ptr(), v_scale.data_ptr(), block_tables.data_ptr<int>(), (int)block_tables.stride(0),
+      tile_seq.data_ptr<int>(), tile_q0.data_ptr<int>(), q_start.data_ptr<int>(), q_len.data_ptr<int>(),
+      ctx_len.data_ptr<int>(), num_tiles, Hq, Hkv, scale_log2, (int)part_tokens, (int)nparts,
+      (int)k_cache.size(0), sem, cur_stream());
+}
+
 // ---- lazily backed KV arenas (vmm.hip)
 bool vmm_supported(int64_t device) { return mlop::vmm_supported((int)device); }
 int64_t vmm_granularity(int64_t device) { return mlop::vmm_granularity((int)device); }
@@ -1054,6 +1138,12 @@ TORCH_LIBRARY(mlop, m) {
         "Tensor k_cache, Tensor v_cache, Tensor block_tables, Tensor tile_seq, Tensor tile_q0, "
         "Tensor q_start, Tensor q_len, Tensor ctx_len, float scale, int part_tokens, "
         "int nparts, int window=0) -> ()");
+  m.def("rope_cache_fp8(Tensor(a!) q_out, Tensor(b!) k_cache, Tensor(c!) v_cache, Tensor(d!) k_scale, "
+        "Tensor(e!) v_scale, Tensor qkv, Tensor pos, Tensor cos_sin, Tensor slots) -> ()");
+  m.def("paged_attention_fp8(Tensor(a!) out, Tensor(b!) part_o, Tensor(c!) part_ml, Tensor(d!) part_sem, Tensor q, "
+        "Tensor k_cache, Tensor v_cache, Tensor k_scale, Tensor v_scale, Tensor block_tables, Tensor tile_seq, "
+        "Tensor tile_q0, Tensor q_start, Tensor q_len, Tensor ctx_len, float scale, int part_tokens, "
+        "int nparts) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(mlop, CUDA, m) {
@@ -1065,6 +1155,8 @@ TORCH_LIBRARY_IMPL(mlop, CUDA, m) {
   m.impl("lora_shrink", &lora_shrink);
   m.impl("lora_expand_add", &lora_expand_add);
   m.impl("paged_attention", &paged_attention);
+  m.impl("rope_cache_fp8", &rope_cache_fp8);
+  m.impl("paged_attention_fp8", &paged_attention_fp8);
   m.impl("flash_prefill", &flash_prefill);
   m.impl("gemm", &gemm);
   m.impl("gemm_ws", &gemm_ws);

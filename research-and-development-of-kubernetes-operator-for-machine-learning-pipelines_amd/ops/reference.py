@@ -44,8 +44,55 @@ def rotate(x, cos, sin):
     return torch.cat([x1 * cos - x2 * sin, x2 * cos + x1 * sin], dim=-1)
 
 
-def rope_cache(qkv, positions, cos_sin, slots, k_cache, v_cache, n_q_heads):
-    """Rotate q/k, scatter k/v into the paged cache, return q [T, Hq, D]."""
+# ------------------------------------------------------------ fp8 KV rows --
+# The fp8 KV cache stores K (after RoPE) and V as OCP e4m3fn with one power-of-two scale per
+# (token, kv head) row.  The scale is 2^e with the smallest integer e such that
+# amax(row) / 2^e <= 448: with amax = m 2^x (frexp, 0.5 <= m < 1), e = x - 9 if m <= 0.875 else
+# x - 8, clamped to [-126, 127]; a zero row takes the smallest exponent.  It is stored as the byte
+# e + 127, and decoded as the fp32 whose bit pattern is byte << 23: 2^(byte - 127) for byte >= 1
+# and 0.0 for byte 0 (the content of a zero-initialised scale tensor), so every byte the kernels
+# can meet is finite.  Integer arithmetic throughout: kv_fp8.hip computes the same byte.
+FP8 = torch.float8_e4m3fn
+FP8_MAX = 448.0
+FP8_EXP_MIN, FP8_EXP_MAX = -126, 127
+
+
+def fp8_row_exponent(amax: torch.Tensor) -> torch.Tensor:
+    """int32 scale exponents of rows with maximum magnitudes ``amax`` (>= 0)."""
+    m, x = torch.frexp(amax.float())
+    e = x - torch.where(m <= 0.875, 9, 8).to(x.dtype)
+    e = torch.where(amax == 0, torch.full_like(e, FP8_EXP_MIN), e)
+    return e.clamp(FP8_EXP_MIN, FP8_EXP_MAX).to(torch.int32)
+
+
+def fp8_scale_decode(scale_bytes: torch.Tensor) -> torch.Tensor:
+    """uint8 scale bytes -> fp32 scales (bit pattern byte << 23)."""
+    return (scale_bytes.to(torch.int32) << 23).view(torch.float32)
+
+
+def fp8_quantize_rows(x: torch.Tensor):
+    """Rows [..., D] -> (e4m3fn [..., D], uint8 scale bytes [...]).  x / 2^e is exact in fp32;
+    the one rounding is the conversion to e4m3fn (nearest even)."""
+    xf = x.float()
+    e = fp8_row_exponent(xf.abs().amax(-1))
+    y = torch.ldexp(xf, -e[..., None]).clamp(-FP8_MAX, FP8_MAX)
+    return y.to(FP8), (e + 127).to(torch.uint8)
+
+
+def fp8_dequantize_rows(x8: torch.Tensor, scale_bytes: torch.Tensor) -> torch.Tensor:
+    """fp32 rows of an e4m3fn tensor [..., D] and its scale bytes [...] (exact)."""
+    return x8.float() * fp8_scale_decode(scale_bytes)[..., None]
+
+
+def fp8_fake_quant(x: torch.Tensor) -> torch.Tensor:
+    """x's rows through the fp8 cache format and back (fp32)."""
+    return fp8_dequantize_rows(*fp8_quantize_rows(x))
+
+
+def rope_cache(qkv, positions, cos_sin, slots, k_cache, v_cache, n_q_heads, k_scale=None, v_scale=None):
+    """Rotate q/k, scatter k/v into the paged cache, return q [T, Hq, D].  An e4m3fn cache takes
+    the rows (rounded to the model dtype as a bf16 cache would hold them) quantised by
+    ``fp8_quantize_rows``, their scale bytes going to ``k_scale`` / ``v_scale`` [NB, Hkv, BS]."""
     T = qkv.shape[0]
     Hkv, BS, D = k_cache.shape[1], k_cache.shape[2], k_cache.shape[3]
     half = D // 2
@@ -55,6 +102,10 @@ def rope_cache(qkv, positions, cos_sin, slots, k_cache, v_cache, n_q_heads):
     q = rotate(x[:, :n_q_heads], cos, sin).to(qkv.dtype)
     k = rotate(x[:, n_q_heads:n_q_heads + Hkv], cos, sin).to(qkv.dtype)
     v = x[:, n_q_heads + Hkv:].to(qkv.dtype)
+    fp8 = k_cache.dtype == FP8
+    if fp8:
+        assert k_scale is not None and v_scale is not None, "an fp8 KV cache needs its scale tensors"
+        (k, ks), (v, vs) = fp8_quantize_rows(k), fp8_quantize_rows(v)
     for t in range(T):
         s = int(slots[t])
         if s < 0:
@@ -62,26 +113,37 @@ def rope_cache(qkv, positions, cos_sin, slots, k_cache, v_cache, n_q_heads):
         b, o = divmod(s, BS)
         k_cache[b, :, o, :] = k[t]
         v_cache[b, :, o, :] = v[t]
+        if fp8:
+            k_scale[b, :, o] = ks[t]
+            v_scale[b, :, o] = vs[t]
     return q
 
 
-def gather_kv(k_cache, v_cache, block_table, n):
-    """Contiguous K, V [n, Hkv, D] of one sequence from its pages."""
+def gather_kv(k_cache, v_cache, block_table, n, k_scale=None, v_scale=None):
+    """Contiguous K, V [n, Hkv, D] of one sequence from its pages (an e4m3fn cache with its scale
+    bytes: the dequantised rows, fp32)."""
     BS = k_cache.shape[2]
     pages = [int(p) for p in block_table[: (n + BS - 1) // BS]]
+    fp8 = k_cache.dtype == FP8
     if not pages:
         Hkv, D = k_cache.shape[1], k_cache.shape[3]
-        z = torch.zeros(0, Hkv, D, dtype=k_cache.dtype, device=k_cache.device)
+        z = torch.zeros(0, Hkv, D, dtype=torch.float32 if fp8 else k_cache.dtype, device=k_cache.device)
         return z, z
-    k = torch.cat([k_cache[p].permute(1, 0, 2) for p in pages], 0)[:n]          # [n, Hkv, D]
-    v = torch.cat([v_cache[p].permute(1, 0, 2) for p in pages], 0)[:n]          # [n, Hkv, D]
+    if fp8:
+        assert k_scale is not None and v_scale is not None, "an fp8 KV cache needs its scale tensors"
+        page = lambda c, sc, p: fp8_dequantize_rows(c[p], sc[p])  # noqa: E731
+    else:
+        page = lambda c, sc, p: c[p]  # noqa: E731
+    k = torch.cat([page(k_cache, k_scale, p).permute(1, 0, 2) for p in pages], 0)[:n]  # [n, Hkv, D]
+    v = torch.cat([page(v_cache, v_scale, p).permute(1, 0, 2) for p in pages], 0)[:n]  # [n, Hkv, D]
     return k, v
 
 
-def paged_attention(q, k_cache, v_cache, meta):
+def paged_attention(q, k_cache, v_cache, meta, k_scale=None, v_scale=None):
     """Causal GQA attention of every query token of ``meta`` over its paged context.  With a
     sliding window ``meta.window = W > 0`` the query at position i attends the keys
-    i - W < j <= i; pages wholly below the first query's window are not read at all."""
+    i - W < j <= i; pages wholly below the first query's window are not read at all.  An e4m3fn
+    cache is read through its scale bytes (``gather_kv``)."""
     W = int(getattr(meta, "window", 0) or 0)
     out = torch.zeros_like(q)
     Hq, D = q.shape[1], q.shape[2]
@@ -100,7 +162,7 @@ def paged_attention(q, k_cache, v_cache, meta):
         # first page any query of the row can see (everything below may have been released)
         BS = k_cache.shape[2]
         lo = max(0, cl[s] - ql[s] - W + 1) // BS * BS if W > 0 else 0
-        k, v = gather_kv(k_cache, v_cache, bt[s][lo // BS:], cl[s] - lo)
+        k, v = gather_kv(k_cache, v_cache, bt[s][lo // BS:], cl[s] - lo, k_scale, v_scale)
         k = k.float().repeat_interleave(G, dim=1)  # [n, Hq, D]
         v = v.float().repeat_interleave(G, dim=1)
         qq = q[qs[s]:qs[s] + ql[s]].float()      # [ql, Hq, D]

@@ -84,6 +84,8 @@ class LLMBackend:
         self._stop = False
         self._thread = threading.Thread(target=self._loop, name="mlop-engine", daemon=True)
         self.steps = 0
+        if metrics is not None:
+            metrics.kv_dtype.labels(**metrics.lv(dtype=self._kv_dtype())).set(1)
         from .gpu_metrics import KernelTimeSampler
 
         # one profiled engine step per period -> mlop_kernel_time_fraction{kernel=...}
@@ -181,9 +183,13 @@ class LLMBackend:
         if params.adapter is not None and params.adapter not in getattr(self.engine, "_adapters", {}):
             raise ValueError(f"unknown adapter {params.adapter!r}")
 
+    def _kv_dtype(self) -> str:
+        return str(getattr(getattr(self.engine, "cfg", None), "kv_cache_dtype", "bf16"))
+
     def metadata(self) -> dict:
         cfg = self.engine.model.cfg
         md = {"name": self.name, "platform": "mlopamd-llm-rocm", "architecture": cfg.name,
+              "kv_cache_dtype": self._kv_dtype(),
               "inputs": [{"name": "text_input", "datatype": "BYTES", "shape": [-1]},
                          {"name": "input_ids", "datatype": "INT64", "shape": [-1]}],
               "outputs": [{"name": "text_output", "datatype": "BYTES", "shape": [-1]},

@@ -37,7 +37,8 @@ import torch
 
 from .. import ops
 from .attn_meta import MetaBuffers, plan_partitions
-from .kv_cache import BLOCK_SIZE, BlockAllocator, KVCache, blocks_for_budget, blocks_needed, prefix_hashes
+from .kv_cache import (BLOCK_SIZE, KV_DTYPES, BlockAllocator, KVCache, blocks_for_budget, blocks_needed,
+                       kv_dtype_bytes, prefix_hashes)
 from .sampler import MAX_LOGPROBS, Sampler, SamplerExt, SamplingParams
 from .tracing import StepTracer, TorchProfileWindow
 
@@ -232,6 +233,11 @@ class EngineConfig:
     # allocated or captured) and the largest adapter rank a slot takes (<= 64)
     max_adapters: int = 0
     max_lora_rank: int = 64
+    # element type of the paged KV cache: "bf16" (the model's dtype), or "fp8" = OCP e4m3fn pages
+    # with one power-of-two scale byte per (token, kv head) row (ops/reference.py "fp8 KV rows"):
+    # 2 D / (D + 1) = 1.98x the pages per byte.  fp8 has no sliding-window, flash-prefill, MoE or
+    # fused-epilogue kernels: those models are rejected, prompt chunks run on the 16-row tiles.
+    kv_cache_dtype: str = "bf16"
 
 
 @dataclass
@@ -315,6 +321,16 @@ class Engine:
         self.device = model.device
         mc = model.cfg
         self.max_model_len = min(cfg.max_model_len, mc.max_position)
+        self._kv_bytes = kv_dtype_bytes(cfg.kv_cache_dtype)  # ValueError for an unknown name
+        self.fp8_kv = cfg.kv_cache_dtype == "fp8"
+        if self.fp8_kv:
+            if int(getattr(mc, "sliding_window", 0) or 0) > 0:
+                raise ValueError('kv_cache_dtype="fp8" does not support sliding-window models '
+                                 f"(sliding_window = {mc.sliding_window}): no windowed fp8 attention kernel")
+            if getattr(mc, "is_moe", False) or model.ps.ep.size > 1:
+                raise ValueError('kv_cache_dtype="fp8" is not supported for MoE models / expert parallelism')
+            if mc.head_dim != 128:
+                raise ValueError('kv_cache_dtype="fp8" needs head_dim 128')
         # multi-LoRA: the slot-major adapter stacks, allocated before the KV pool is sized from
         # what is left (raises for Mixtral / TP > 1 / EP)
         self.lora = None
@@ -340,8 +356,8 @@ class Engine:
             nb = int(t.item())
         t_kv = time.perf_counter()
         # TP ranks must all hold every page id the leader hands out: eager backing there
-        self.kv = KVCache(mc.num_layers, nb, model.n_kv, mc.head_dim, self.device, model.dtype,
-                          lazy=False if tp.size > 1 else None)
+        self.kv = KVCache(mc.num_layers, nb, model.n_kv, mc.head_dim, self.device,
+                          KV_DTYPES[cfg.kv_cache_dtype][0] or model.dtype, lazy=False if tp.size > 1 else None)
         if self.device.type == "cuda":
             torch.cuda.synchronize(self.device)
         kv_alloc_ms = int(1e3 * (time.perf_counter() - t_kv))
@@ -354,7 +370,10 @@ class Engine:
         self.meta = MetaBuffers(max(cfg.max_num_batched_tokens, cfg.max_num_seqs),
                                 cfg.max_num_seqs + self.buckets[-1], self.max_blocks_per_seq,
                                 self.G, model.n_kv, self.max_model_len, self.device,
-                                window=getattr(mc, "sliding_window", 0))
+                                window=getattr(mc, "sliding_window", 0),
+                                # fp8 pages have no flash-prefill kernel: every row on the 16-row tiles
+                                # (the route G > 8 takes)
+                                **({"flash_min_q": 1 << 30} if self.fp8_kv else {}))
         self.window = self.meta.window
         self._swa = self.window > 0 and cfg.swa_release
         self.free_rows = list(range(cfg.max_num_seqs - 1, -1, -1))
@@ -405,6 +424,10 @@ class Engine:
         self.graph_pool = None
         self.stats = collections.Counter()
         self.stats["kv_pages_released"] = 0
+        if self.fp8_kv:
+            # (only when it is not the default: the other entries are counters that callers
+            # difference between two readings; read it as stats.get("kv_cache_dtype", "bf16"))
+            self.stats["kv_cache_dtype"] = cfg.kv_cache_dtype
         # one-step-ahead (async) scheduling state: the in-flight step, its token read-back
         # buffers (two pinned, alternating) and the event after its metadata upload.  Under TP
         # only the leader schedules (workers follow the host-side headers, StepSync); under EP
@@ -487,7 +510,7 @@ class Engine:
             budget = 64 * 2**20
         need = int(self.cfg.kv_fraction * self.cfg.max_num_seqs *
                    blocks_needed(min(self.cfg.max_model_len, mc.max_position))) + 2
-        nb = blocks_for_budget(budget, mc.num_layers, m.n_kv, mc.head_dim)
+        nb = blocks_for_budget(budget, mc.num_layers, m.n_kv, mc.head_dim, *self._kv_bytes)
         return int(min(nb, need))
 
     # -------------------------------------------------------- requests --

@@ -6,6 +6,13 @@ Device side: one K and one V tensor per layer, pages of 16 tokens:
                                           store; attention.hip reads V^T out of LDS transposed)
 zeroed before first use (the attention kernel relies on finite unused slots).
 
+fp8 mode (``dtype=torch.float8_e4m3fn``; ``EngineConfig.kv_cache_dtype = "fp8"``): the pages hold
+OCP e4m3fn bytes in the same shape, and every (token, kv head) row has one scale byte
+(ops/reference.py "fp8 KV rows") in
+  k_scale[layer], v_scale[layer] : [num_blocks, Hkv, 16]  uint8
+The scale tensors (1/128 of the pages) are always allocated eagerly and zeroed - before any
+page id is handed out - also beside a lazily backed page arena: byte 0 decodes to scale 0.0.
+
 Two ways to back it:
 
 * eager: two ``torch.empty`` + ``zero_`` (CPU, TP ranks, ``kv_cache.LAZY = False``);
@@ -29,6 +36,8 @@ import time
 import numpy as np
 import torch
 
+from ..models.config import kv_dtype_bytes  # noqa: F401  (re-exported: the engine sizes pages with it)
+
 BLOCK_SIZE = 16
 CHUNK_BYTES_PER_REGION = 64 << 20   # lazy backing unit: 64 MB of each K / V layer tensor
 INITIAL_BYTES = 4 << 30             # backed before ready (all layers, K and V)
@@ -40,6 +49,11 @@ def _sync(device) -> None:
 
 
 LAZY = True  # GPU pools lazily backed (tests flip it for the eager / lazy A/B)
+
+FP8 = torch.float8_e4m3fn
+# kv_cache_dtype name -> (torch dtype of the pages; None: the model's); its bytes per element and
+# scale bytes per row: models.config.kv_dtype_bytes
+KV_DTYPES = {"bf16": (None,), "fp8": (FP8,)}
 
 
 def _lazy_default(device) -> bool:
@@ -58,6 +72,7 @@ class KVCache:
         self.num_layers, self.num_blocks = num_layers, num_blocks
         self.num_kv_heads, self.head_dim = num_kv_heads, head_dim
         self.device, self.dtype = torch.device(device), dtype
+        self.fp8 = dtype == FP8
         self.lazy = _lazy_default(device) if lazy is None else lazy
         self.fill_failed = False  # a background chunk could not be backed: stop growing
         self._flat = None
@@ -66,18 +81,31 @@ class KVCache:
             self._init_lazy(initial_blocks)
             self.timing_ms = {"kv_malloc_ms": int(1e3 * (time.perf_counter() - t0)), "kv_zero_ms": 0}
         else:
+            # (fp8 pages are allocated and zeroed as bytes, then viewed: byte 0 is +0.0)
+            raw = torch.uint8 if self.fp8 else dtype
             self.k_all = torch.empty(num_layers, num_blocks, num_kv_heads, BLOCK_SIZE, head_dim,
-                                     device=device, dtype=dtype)
+                                     device=device, dtype=raw)
             self.v_all = torch.empty(num_layers, num_blocks, num_kv_heads, BLOCK_SIZE, head_dim,
-                                     device=device, dtype=dtype)
+                                     device=device, dtype=raw)
             _sync(device)
             t1 = time.perf_counter()
             self.k_all.zero_()
             self.v_all.zero_()
             _sync(device)
+            if self.fp8:
+                self.k_all, self.v_all = self.k_all.view(FP8), self.v_all.view(FP8)
             self.timing_ms = {"kv_malloc_ms": int(1e3 * (t1 - t0)), "kv_zero_ms": int(1e3 * (time.perf_counter() - t1))}
         self.k = [self.k_all[i] for i in range(num_layers)]
         self.v = [self.v_all[i] for i in range(num_layers)]
+        self.k_scale_all = self.v_scale_all = None
+        self.k_scale = self.v_scale = [None] * num_layers
+        if self.fp8:
+            self.k_scale_all, self.v_scale_all = (
+                torch.zeros(num_layers, num_blocks, num_kv_heads, BLOCK_SIZE, device=device, dtype=torch.uint8)
+                for _ in range(2))
+            _sync(device)
+            self.k_scale = [self.k_scale_all[i] for i in range(num_layers)]
+            self.v_scale = [self.v_scale_all[i] for i in range(num_layers)]
 
     def _init_lazy(self, initial_blocks):
         L, Hkv, D = self.num_layers, self.num_kv_heads, self.head_dim
@@ -144,18 +172,26 @@ class KVCache:
             self.fill_failed = True
         return min(self.num_blocks, int(torch.ops.mlop.vmm_chunks_ready(self._flat)) * self.chunk_blocks)
 
+    def scales(self, layer: int) -> dict:
+        """The ``k_scale`` / ``v_scale`` keyword arguments of ops.rope_cache / ops.paged_attention
+        for a layer's pages (none for a bf16 cache)."""
+        return {"k_scale": self.k_scale[layer], "v_scale": self.v_scale[layer]} if self.fp8 else {}
+
     @staticmethod
-    def bytes_per_block(num_layers, num_kv_heads, head_dim, dtype_bytes=2) -> int:
-        return 2 * num_layers * num_kv_heads * BLOCK_SIZE * head_dim * dtype_bytes
+    def bytes_per_block(num_layers, num_kv_heads, head_dim, dtype_bytes=2, scale_bytes=0) -> int:
+        """Bytes of one page id over all layers, K and V; ``scale_bytes`` per (token, kv head) row
+        (fp8: ``kv_dtype_bytes("fp8")`` = (1, 1))."""
+        return 2 * num_layers * num_kv_heads * BLOCK_SIZE * (head_dim * dtype_bytes + scale_bytes)
 
     @property
     def nbytes(self) -> int:
-        return 2 * self.num_layers * self.num_blocks * self.num_kv_heads * BLOCK_SIZE * self.head_dim * \
-            self.k_all.element_size()
+        return self.num_blocks * self.bytes_per_block(self.num_layers, self.num_kv_heads, self.head_dim,
+                                                      self.k_all.element_size(), 1 if self.fp8 else 0)
 
 
-def blocks_for_budget(budget_bytes: int, num_layers, num_kv_heads, head_dim, dtype_bytes=2) -> int:
-    return max(1, budget_bytes // KVCache.bytes_per_block(num_layers, num_kv_heads, head_dim, dtype_bytes))
+def blocks_for_budget(budget_bytes: int, num_layers, num_kv_heads, head_dim, dtype_bytes=2, scale_bytes=0) -> int:
+    return max(1, budget_bytes // KVCache.bytes_per_block(num_layers, num_kv_heads, head_dim, dtype_bytes,
+                                                          scale_bytes))
 
 
 class BlockAllocator:

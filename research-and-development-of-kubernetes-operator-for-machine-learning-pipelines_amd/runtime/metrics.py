@@ -76,6 +76,9 @@ class RuntimeMetrics:
         self.kv_fill_failed = Gauge("mlop_kv_cache_fill_failed",
                                     "1 when the background KV fill could not back a chunk (serving continues "
                                     "on the pages already backed)", base, registry=r)
+        # info-style: constant 1, the engine's kv_cache_dtype ("bf16" / "fp8") as the label
+        self.kv_dtype = Gauge("mlop_kv_cache_dtype_info", "KV cache element type of the engine (label dtype)",
+                              base + ["dtype"], registry=r)
         self.ready = Gauge("mlop_ready", "1 when the model is loaded and graphs captured", base, registry=r)
         self.load_seconds = Gauge("mlop_model_load_seconds", "Start-up time to ready", base, registry=r)
         self.gpu_busy = Gauge("mlop_gpu_busy_percent", "GPU busy %", base + ["gpu"], registry=r)

@@ -46,8 +46,14 @@ ap.add_argument("--fused-combine", action="store_true",
                 help="split-KV launches combine in the launch (tickets), as the engine's; default: reduce launch")
 ap.add_argument("--cases", default=os.environ.get("CASES", "2048x384,1024x384,256x1024,64x4096,8x8192"),
                 help="comma-separated BxL")
+ap.add_argument("--kv-dtype", default="bf16", choices=["bf16", "fp8", "both"],
+                help="KV cache format; both: the bf16 and the fp8 kernel interleaved round by round on the same "
+                     "metadata (the fp8 pages are the quantised bf16 pages), with the run-to-run spread of each")
+ap.add_argument("--rounds", type=int, default=3, help="timed rounds per format (each 10 launches; min and spread reported)")
 args = ap.parse_args()
 W = args.window
+if W and args.kv_dtype != "bf16":
+    sys.exit("the fp8 cache has no sliding-window kernel")
 cases = [(int(b), int(l)) for b, l in (c.split("x") for c in args.cases.split(","))]
 for B, L in cases:
     np.random.seed(0)
@@ -65,8 +71,23 @@ for B, L in cases:
     if nparts > 1 and args.fused_combine:  # the in-launch combine, as the engine runs it
         m.part_sem = torch.zeros(B * Hkv, dtype=torch.int32, device=dev)
     q = torch.randn(T, Hq, D, device=dev, dtype=bf)
-    t = min(timeit(lambda: ops.paged_attention(q, kc, vc, m)) for _ in range(3))
     keys = sum(c - (max(0, c - W) & ~31) for c in ctx) if W else sum(ctx)  # from the window's page pair
-    byts = keys * Hkv * D * 2 * 2
-    print(json.dumps(dict(B=B, window=W, mean_ctx=round(float(np.mean(ctx)), 1), nparts=nparts, us=round(t, 1),
-                          kv_gb=round(byts / 1e9, 3), tbps=round(byts / t / 1e6, 2))), flush=True)
+    runs = {}
+    if args.kv_dtype in ("bf16", "both"):
+        runs["bf16"] = (lambda: ops.paged_attention(q, kc, vc, m), keys * Hkv * D * 2 * 2)
+    if args.kv_dtype in ("fp8", "both"):
+        k8, ks = ops.ref.fp8_quantize_rows(kc)
+        v8, vs = ops.ref.fp8_quantize_rows(vc)
+        if args.kv_dtype == "fp8":
+            del kc, vc
+        runs["fp8"] = (lambda: ops.paged_attention(q, k8, v8, m, k_scale=ks, v_scale=vs), keys * Hkv * (D + 1) * 2)
+    times = {d: [] for d in runs}
+    for _ in range(args.rounds):  # interleaved: one round of each format after the other
+        for d, (fn, _) in runs.items():
+            times[d].append(timeit(fn))
+    for d, (_, byts) in runs.items():
+        t, ts = min(times[d]), sorted(times[d])
+        print(json.dumps(dict(B=B, kv_dtype=d, window=W, mean_ctx=round(float(np.mean(ctx)), 1), nparts=nparts,
+                              us=round(t, 1), us_rounds=[round(x, 1) for x in times[d]],
+                              spread_pct=round(100 * (ts[-1] - ts[0]) / ts[0], 2),
+                              kv_gb=round(byts / 1e9, 3), tbps=round(byts / t / 1e6, 2))), flush=True)
