@@ -1040,10 +1040,10 @@ def ws_on():
     torch.ops.mlop.gemm_ws_max_m(64)
     yield
     torch.ops.mlop.gemm_ws_max_m(prev)
-    torch.ops.mlop.gemm_ws_plan(0, 0, 1)
+    torch.ops.mlop.gemm_ws_plan(0, 0, 0)  # the source default (gemm_ws.hip g_ws_rb / g_ws_u / g_ws_nt)
 
 
-@pytest.mark.parametrize("plan", [(0, 0, 1), (4, 4, 0), (2, 8, 1)], ids=["default", "rb4u4c", "rb2u8nt"])
+@pytest.mark.parametrize("plan", [(0, 0, 0), (0, 0, 1), (4, 4, 0), (2, 8, 1)], ids=["default", "nt", "rb4u4c", "rb2u8nt"])
 @pytest.mark.parametrize("M", [5, 16, 17, 33, 64])
 @pytest.mark.parametrize("N,K,epi", [(1024, 4096, 0), (2048, 4096, 1), (512, 14336, 0), (4096, 1024, 0)])
 def test_gemm_ws_vs_fp32(gpu, ws_on, plan, M, N, K, epi):
