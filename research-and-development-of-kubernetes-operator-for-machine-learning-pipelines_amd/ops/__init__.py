@@ -965,8 +965,10 @@ def grouped_gemm(xp, w, offsets, epi: int = EPI_NONE, avg_rows: int | None = Non
     (tiles enumerate (group, m-tile) pairs on device: no host sync, graph-safe).  ``a_rows``
     [R]: permuted row r is row a_rows[r] of xp (R output rows; moe_dispatch_mid)."""
     if a_rows is not None and not xp.is_cuda:
-        xp = xp[a_rows.long()]
-        a_rows = None
+        n = int(offsets[-1])  # the entries behind the valid rows are never read, as on the GPU
+        rows = torch.zeros(a_rows.numel(), xp.shape[1], dtype=xp.dtype)
+        rows[:n] = xp[a_rows[:n].long()]
+        xp, a_rows = rows, None
     if not xp.is_cuda:
         y = ref.grouped_gemm(xp, w, offsets)
         return ref.silu_mul(deinterleave_cols(y)) if epi == EPI_SILU_MUL else y

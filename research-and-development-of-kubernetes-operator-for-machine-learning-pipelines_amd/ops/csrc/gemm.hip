@@ -402,14 +402,17 @@ __global__ void __launch_bounds__(WM * WN * 64) gemm_kernel(
   }
 }
 
-// sum the split-K slabs and apply the epilogue; one thread per 8 outputs
+// sum the split-K slabs and apply the epilogue; one thread per 8 outputs.  m_valid (grouped:
+// offsets + n_groups, the routed rows of this launch; M stays the slab stride): the rows behind
+// it hold no product - their slab rows were never written - and are neither read nor stored
 template <int EPI>
 __global__ void __launch_bounds__(256) splitk_reduce_kernel(uint16_t* __restrict__ C, int ldc,
                                                            const float* __restrict__ ws, int M,
-                                                           int N, int splits) {
+                                                           int N, int splits,
+                                                           const int* __restrict__ m_valid) {
   const int outw = EPI == EPI_NONE ? N : N / 2;
   const int vpr = outw / 8;
-  const long total = (long)M * vpr;
+  const long total = (long)(m_valid != nullptr ? min(*m_valid, M) : M) * vpr;
   for (long v = blockIdx.x * (long)blockDim.x + threadIdx.x; v < total;
        v += (long)gridDim.x * blockDim.x) {
     const int r = (int)(v / vpr), j0 = (int)(v % vpr) * 8;
@@ -1228,12 +1231,12 @@ static GemmCall gemm_call(int op, int M, int N, int K, int lda, int ldb, int ldc
 }
 
 static void launch_splitk_reduce(int epi, uint16_t* C, int ldc, const float* ws, int M, int N, int splits,
-                                 hipStream_t st) {
+                                 hipStream_t st, const int* m_valid = nullptr) {
   const int outw = epi == EPI_NONE ? N : N / 2;
   const long total = (long)M * (outw / 8);
   const int g = (int)std::min<long>((total + 255) / 256, 4096);
-  if (epi == EPI_NONE) splitk_reduce_kernel<EPI_NONE><<<g, 256, 0, st>>>(C, ldc, ws, M, N, splits);
-  else splitk_reduce_kernel<EPI_SILU_MUL><<<g, 256, 0, st>>>(C, ldc, ws, M, N, splits);
+  if (epi == EPI_NONE) splitk_reduce_kernel<EPI_NONE><<<g, 256, 0, st>>>(C, ldc, ws, M, N, splits, m_valid);
+  else splitk_reduce_kernel<EPI_SILU_MUL><<<g, 256, 0, st>>>(C, ldc, ws, M, N, splits, m_valid);
 }
 
 // QKV + RoPE + cache stores on route rt (not refused)
@@ -1393,7 +1396,8 @@ void launch_grouped_gemm(const void* A, const void* B, void* C, const int* offse
     *defer_ws = ws;
     *defer_splits = rt.splits;
   } else if (rt.finish == FIN_REDUCE) {
-    launch_splitk_reduce(epi, (uint16_t*)C, epi == EPI_NONE ? N : N / 2, ws, M, N, rt.splits, st);
+    launch_splitk_reduce(epi, (uint16_t*)C, epi == EPI_NONE ? N : N / 2, ws, M, N, rt.splits, st,
+                         offsets + n_groups);
   }
 }
 

@@ -181,8 +181,11 @@ def paged_attention(q, k_cache, v_cache, meta, k_scale=None, v_scale=None):
 # ------------------------------------------------------------------ MoE --
 
 def moe_route(logits, top_k):
+    """softmax -> top-k -> renormalise.  Ties go to the lower expert index, as in the HIP routes
+    (strict > over ascending e): a stable descending sort, where torch.topk promises no order."""
     p = torch.softmax(logits.float(), dim=-1)
-    w, idx = torch.topk(p, top_k, dim=-1)
+    w, idx = torch.sort(p, dim=-1, descending=True, stable=True)
+    w, idx = w[..., :top_k], idx[..., :top_k]
     w = w / w.sum(-1, keepdim=True)
     return w, idx.to(torch.int32)
 
