@@ -203,7 +203,7 @@ def paged_attention(q, k_cache, v_cache, meta, out: torch.Tensor | None = None,
     """Ragged paged attention; ``meta`` is a ``mlopamd.runtime.attn_meta.AttnMeta``.
     Decode / short rows run on the 16-q-row tiles (``tile_*``), prompt chunks on
     the flash-prefill tiles (``ptile_*``); both write disjoint rows of ``out``.
-    An e4m3fn cache (with its scale bytes) runs attention_fp8.hip's kernel on the 16-row
+    An e4m3fn cache (with its scale bytes) runs the same decode kernel (KvFp8) on the 16-row
     tiles only: no sliding window and no flash tiles (a missing kernel is an error)."""
     fp8 = _fp8_scales(k_cache, k_scale, v_scale)
     if not q.is_cuda:

@@ -96,21 +96,214 @@ __device__ __forceinline__ int wid_of(unsigned t) { return __builtin_amdgcn_read
 // block-table walk and the combine's slab count are all relative to it.
 __device__ __forceinline__ int window_kv_lo(int p0, int window) { return max(0, p0 - window + 1) & ~31; }
 
+// ---- KV formats of the decode kernel.  A policy type carries what differs between them, in the
+// order the page-pair loop meets it: the cache pointers, the Q fragment order (q_dim), the pair's
+// K fragments (load_k), the V issue behind the K loads (issue_v), making the wave's bf16 V image
+// readable (v_ready), and the per-token factors on S and p (kScaled: k_scale, v_scale).  Pair is
+// what a lane holds of the pair in flight between those steps.
+
+// bf16 pages: K straight into the fragments, V by LDS-DMA into the wave's image
+struct KvBf16 {
+  const uint16_t* kc;
+  const uint16_t* vc;
+  static constexpr bool kScaled = false;
+  struct Pair {};
+  static __device__ __forceinline__ int q_dim(int kk, int g4) { return kk * 32 + g4 * 8; }
+  template <int NT>
+  __device__ __forceinline__ void load_k(Pair&, int pgA, int pgB, size_t page_stride, int kvh, int lane,
+                                         bf16x8 (&ka)[4], bf16x8 (&kb)[4]) const {
+    const int r = lane & 15, g4 = lane >> 4;
+    const uint16_t* kA = kc + pgA * page_stride + (size_t)kvh * kBS * kD;
+    const uint16_t* kB = kc + pgB * page_stride + (size_t)kvh * kBS * kD;
+    // K rows of MFMA row r: pair tokens 8*(r>>2) + (r&3) (first S MFMA) and +4 (second)
+    const uint16_t* kR = (r >> 3 ? kB : kA) + (8 * ((r >> 2) & 1) + (r & 3)) * kD;
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) {
+      if constexpr ((NT & 1) != 0) {
+        ka[kk] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(kR + kk * 32 + g4 * 8));
+        kb[kk] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(kR + 4 * kD + kk * 32 + g4 * 8));
+      } else {
+        ka[kk] = *reinterpret_cast<const bf16x8*>(kR + kk * 32 + g4 * 8);
+        kb[kk] = *reinterpret_cast<const bf16x8*>(kR + 4 * kD + kk * 32 + g4 * 8);
+      }
+    }
+  }
+  // the pair's 32 token rows of this kv head by LDS-DMA into this wave's V image (the S MFMAs
+  // wait for the K loads only; the previous pair's transposed reads are complete: their MFMAs
+  // consumed them)
+  template <int NT>
+  __device__ __forceinline__ void issue_v(Pair&, int pgA, int pgB, size_t page_stride, int kvh, int lane,
+                                          uint32_t vimg) const {
+    const int r = lane & 15, g4 = lane >> 4;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    const uint16_t* vA = vc + pgA * page_stride + (size_t)kvh * kBS * kD;
+    const uint16_t* vB = vc + pgB * page_stride + (size_t)kvh * kBS * kD;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int trow = (4 * i + g4) & 15;
+      const uint16_t* src = (i < 4 ? vA : vB) + trow * kD + ((r ^ vswz(trow)) << 3);
+      __builtin_amdgcn_global_load_lds((const void*)src, (lds_void_t*)(uintptr_t)(vimg + 1024u * i), 16, 0,
+                                       (NT & 1) ? 2 /* nt */ : 0);
+    }
+  }
+  __device__ __forceinline__ void v_ready(const Pair&, int, uint32_t) const {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's V image has landed
+  }
+  __device__ __forceinline__ void v_read_done() const {}
+};
+
+// fp8 pages (kv_fp8.hip's e4m3fn pages and scale bytes).  Q and P stay bf16 and the MFMAs
+// 16x16x32 bf16: K and V fragments are converted e4m3 -> bf16 in registers (exact: e4m3 has 3
+// mantissa bits and a narrower exponent range), so the only error of the fp8 cache is the
+// quantisation of the stored rows.  The row scales are powers of two and are folded in exactly:
+// S *= 2^e_k on the accumulator, p *= 2^e_v on the way to the bf16 P fragment, AFTER l has summed
+// the unscaled p.
+//
+// K: an fp8 fragment and a bf16 fragment of this MFMA both hold 8 consecutive k per lane, so
+// the conversion is lane-local.  Lane (r, g4) loads bytes 16 g4 .. +15 and 64 + 16 g4 .. +15 of
+// its token row (two 16-B loads; a row's four lanes read whole 64-B runs): k-step kk holds
+// dims 64 (kk >> 1) + 16 g4 + 8 (kk & 1) .. +7, and Q is loaded in the same order (the
+// contraction order over d is free).
+// V: loaded to VGPRs (16 B = 16 dims of one token row per lane and load), converted, and
+// written with ds_write_b128 into the bf16 image vt_frag reads transposed: row t at 256 t, 16-B
+// chunk c at slot c ^ vswz(t).  (The 8-bit transposed read of a 128-B-row fp8 image would halve
+// the LDS traffic; profiles/fp8_kv.md says why it is not used.)
+//
+// REQUIREMENT, as for bf16: pages AND scale rows are zero-initialised at allocation.  Byte 0 is
+// +0.0 as e4m3 and scale 0.0, and every byte the writer stores is finite; a scale byte 255
+// (+inf) is never written.
+typedef __attribute__((address_space(3))) u32x4 lds_u32x4;
+
+// 8 consecutive e4m3fn bytes -> one bf16 fragment: v_cvt_pk_f32_fp8 per byte pair, then the
+// high halves of the two floats in one v_perm_b32 (the conversion to bf16 drops zero bits only)
+__device__ __forceinline__ bf16x8 cvt8(uint32_t w0, uint32_t w1) {
+  const auto f0 = __builtin_amdgcn_cvt_pk_f32_fp8((int)w0, false);
+  const auto f1 = __builtin_amdgcn_cvt_pk_f32_fp8((int)w0, true);
+  const auto f2 = __builtin_amdgcn_cvt_pk_f32_fp8((int)w1, false);
+  const auto f3 = __builtin_amdgcn_cvt_pk_f32_fp8((int)w1, true);
+  u32x4 o;
+  o[0] = __builtin_amdgcn_perm(__float_as_uint(f0[1]), __float_as_uint(f0[0]), 0x07060302u);
+  o[1] = __builtin_amdgcn_perm(__float_as_uint(f1[1]), __float_as_uint(f1[0]), 0x07060302u);
+  o[2] = __builtin_amdgcn_perm(__float_as_uint(f2[1]), __float_as_uint(f2[0]), 0x07060302u);
+  o[3] = __builtin_amdgcn_perm(__float_as_uint(f3[1]), __float_as_uint(f3[0]), 0x07060302u);
+  return __builtin_bit_cast(bf16x8, o);
+}
+
+// scale byte i of a dword of four -> the fp32 with bit pattern byte << 23 (kv_fp8.hip)
+__device__ __forceinline__ float scale_of(uint32_t w, int i) {
+  return __uint_as_float(((w >> (8 * i)) & 0xffu) << 23);
+}
+
+template <bool NT>
+__device__ __forceinline__ u32x4 load16(const uint8_t* p) {
+  if constexpr (NT) return __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
+  else return *reinterpret_cast<const u32x4*>(p);
+}
+
+struct KvFp8 {
+  const uint8_t* kc;
+  const uint8_t* vc;
+  const uint8_t* ksc;  // scale bytes [NB, Hkv, 16]
+  const uint8_t* vsc;
+  int srow_stride;     // scale bytes per page: Hkv * 16
+  static constexpr bool kScaled = true;
+  struct Pair {
+    u32x2 ksw, vsw;  // the scales of this lane's 8 consecutive pair tokens 8 g4 .. +7
+    u32x4 vr[4];     // V load j: image row 8 j + (lane >> 3), bytes 16 (lane & 7) .. +15 of the row
+  };
+  // Q in the K loads' d order
+  static __device__ __forceinline__ int q_dim(int kk, int g4) { return 64 * (kk >> 1) + 16 * g4 + 8 * (kk & 1); }
+  template <int NT>
+  __device__ __forceinline__ void load_k(Pair& pr, int pgA, int pgB, size_t page_stride, int kvh, int lane,
+                                         bf16x8 (&ka)[4], bf16x8 (&kb)[4]) const {
+    const int r = lane & 15, g4 = lane >> 4;
+    const uint8_t* kA = kc + pgA * page_stride + (size_t)kvh * kBS * kD;
+    const uint8_t* kB = kc + pgB * page_stride + (size_t)kvh * kBS * kD;
+    // K rows of MFMA row r: pair tokens 8*(r>>2) + (r&3) (first S MFMA) and +4 (second)
+    const uint8_t* kR = (r >> 3 ? kB : kA) + (8 * ((r >> 2) & 1) + (r & 3)) * kD + 16 * g4;
+    const u32x4 ka0 = load16<(NT & 1) != 0>(kR), ka1 = load16<(NT & 1) != 0>(kR + 64);
+    const u32x4 kb0 = load16<(NT & 1) != 0>(kR + 4 * kD), kb1 = load16<(NT & 1) != 0>(kR + 4 * kD + 64);
+    // 8 contiguous scale bytes (pages and scale rows are addressed by the same clamped id)
+    const size_t srow = (size_t)(g4 >> 1 ? pgB : pgA) * srow_stride + (size_t)kvh * kBS + 8 * (g4 & 1);
+    pr.ksw = *reinterpret_cast<const u32x2*>(ksc + srow);
+    pr.vsw = *reinterpret_cast<const u32x2*>(vsc + srow);
+    ka[0] = cvt8(ka0[0], ka0[1]); ka[1] = cvt8(ka0[2], ka0[3]);
+    ka[2] = cvt8(ka1[0], ka1[1]); ka[3] = cvt8(ka1[2], ka1[3]);
+    kb[0] = cvt8(kb0[0], kb0[1]); kb[1] = cvt8(kb0[2], kb0[3]);
+    kb[2] = cvt8(kb1[0], kb1[1]); kb[3] = cvt8(kb1[2], kb1[3]);
+  }
+  // this pair's V rows into registers, issued behind the K loads
+  template <int NT>
+  __device__ __forceinline__ void issue_v(Pair& pr, int pgA, int pgB, size_t page_stride, int kvh, int lane,
+                                          uint32_t) const {
+    const int v_row = lane >> 3, v_c8 = lane & 7;
+    const uint8_t* vA = vc + pgA * page_stride + (size_t)kvh * kBS * kD + v_row * kD + 16 * v_c8;
+    const uint8_t* vB = vc + pgB * page_stride + (size_t)kvh * kBS * kD + v_row * kD + 16 * v_c8;
+    pr.vr[0] = load16<(NT & 1) != 0>(vA);
+    pr.vr[1] = load16<(NT & 1) != 0>(vA + 8 * kD);
+    pr.vr[2] = load16<(NT & 1) != 0>(vB);
+    pr.vr[3] = load16<(NT & 1) != 0>(vB + 8 * kD);
+  }
+  // the bf16 image (rows 0-15 page A, 16-31 page B; a lane's 16 bytes are bf16 chunks
+  // 2 (lane & 7) and + 1): a wave's LDS operations execute in order, so these writes follow the
+  // previous pair's transposed reads and precede this pair's without a barrier
+  __device__ __forceinline__ void v_ready(const Pair& pr, int lane, uint32_t vimg) const {
+    const int v_row = lane >> 3, v_c8 = lane & 7;
+    const uint32_t v_dst = vimg + 256u * v_row;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int sw = vswz((8 * j + v_row) & 15);
+      const uint32_t a = v_dst + 2048u * j;
+      *(lds_u32x4*)(uintptr_t)(a + 16u * ((2 * v_c8) ^ sw)) = __builtin_bit_cast(u32x4, cvt8(pr.vr[j][0], pr.vr[j][1]));
+      *(lds_u32x4*)(uintptr_t)(a + 16u * ((2 * v_c8 + 1) ^ sw)) = __builtin_bit_cast(u32x4, cvt8(pr.vr[j][2], pr.vr[j][3]));
+    }
+    asm volatile("" ::: "memory");
+  }
+  // the next pair's image writes stay behind this pair's transposed reads
+  __device__ __forceinline__ void v_read_done() const { asm volatile("" ::: "memory"); }
+  static __device__ __forceinline__ float k_scale(const Pair& pr, int h, int i) { return scale_of(pr.ksw[h], i); }
+  static __device__ __forceinline__ float v_scale(const Pair& pr, int h, int i) { return scale_of(pr.vsw[h], i); }
+};
+
+// the split-KV combine of one output row's 8 dims c .. c + 7 (dst): slabs 0 .. nvalid - 1 of a
+// (tile, kv head), whose first slab is `base`, row rr of each.  The in-launch tail of
+// paged_attn_kernel and attn_reduce_kernel both end here.
+__device__ __forceinline__ void combine_slabs(uint16_t* dst, const float* part_o, const float* part_ml,
+                                              size_t base, int nvalid, int rr, int c) {
+  float M = kNegBig;
+  for (int p = 0; p < nvalid; ++p) M = fmaxf(M, part_ml[((base + p) * 16 + rr) * 2]);
+  float L = 0.f, acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  for (int p = 0; p < nvalid; ++p) {
+    const size_t pb = (base + p) * 16 + rr;
+    const float f = exp2f(part_ml[pb * 2] - M);
+    L += f * part_ml[pb * 2 + 1];
+    const float4* po = reinterpret_cast<const float4*>(part_o + pb * kD + c);
+    const float4 x0 = po[0], x1 = po[1];
+    acc[0] += f * x0.x; acc[1] += f * x0.y; acc[2] += f * x0.z; acc[3] += f * x0.w;
+    acc[4] += f * x1.x; acc[5] += f * x1.y; acc[6] += f * x1.z; acc[7] += f * x1.w;
+  }
+  const float inv = L > 0.f ? 1.f / L : 0.f;
+  u32x4 ov;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) ov[j] = pack2(acc[2 * j] * inv, acc[2 * j + 1] * inv);
+  *reinterpret_cast<u32x4*>(dst) = ov;
+}
+
 // NT bit 0: K / V loads non-temporal, bit 1: the output stores.  WIN: sliding-window attention
-// (query i attends keys i - window < j <= i, window > 0); false compiles the window out.
-template <int G, int NT, bool WIN = false>
+// (query i attends keys i - window < j <= i, window > 0); false compiles the window out (bf16
+// only: no WIN instantiation over KvFp8 exists yet).
+template <int G, int NT, bool WIN, class KV>
 __global__ void __launch_bounds__(256) paged_attn_kernel(
     uint16_t* __restrict__ out, float* __restrict__ part_o, float* __restrict__ part_ml,
-    const uint16_t* __restrict__ q, const uint16_t* __restrict__ kc,
-    const uint16_t* __restrict__ vc, const int* __restrict__ block_tables, int bt_stride,
+    const uint16_t* __restrict__ q, const KV kv, const int* __restrict__ block_tables, int bt_stride,
     const int* __restrict__ tile_seq, const int* __restrict__ tile_q0,
     const int* __restrict__ q_start, const int* __restrict__ q_len,
     const int* __restrict__ ctx_len, int Hq, int Hkv, float scale_log2, int part_tokens,
     int nparts, int num_blocks, int* __restrict__ sem, int window) {
   constexpr int QT = 16 / G;
-  // (3 waves per SIMD at 134 VGPRs; forcing 4 (127 VGPRs, amdgpu_waves_per_eu) measured the
-  // same on every decode shape and the headline, scripts/history/r4_occ.sh)
-  // wave w stages its page pair's V image (2 x 16 token rows x 256 B = 8 KB) inside sm_o[w]
+  // (3 waves per SIMD at 134 VGPRs, fp8 164; forcing 4 (127 VGPRs, amdgpu_waves_per_eu) measured
+  // the same on every bf16 decode shape and the headline, scripts/history/r4_occ.sh)
+  // wave w stages its page pair's bf16 V image (2 x 16 token rows x 256 B = 8 KB) inside sm_o[w]
   // (8448 B, 256-B aligned: vt_frag), which it alone writes after its loop.  (A second image per
   // wave, prefetching the next pair, measured 1-4 % SLOWER on every decode shape: r04 profile.)
   __shared__ __attribute__((aligned(256))) float sm_o[4][16][kD + 4];
@@ -160,12 +353,12 @@ __global__ void __launch_bounds__(256) paged_attn_kernel(
   const int head = kvh * G + (r % G);
   const int pos_r = row_ok ? ctx - ql + qi : -1;
 
-  bf16x8 qf[4];
+  bf16x8 qf[4];  // k-step kk in the d order of the format's K fragments
   {
     const uint16_t* qrow = q + ((size_t)(qs + (row_ok ? qi : 0)) * Hq + head) * kD;
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk) {
-      bf16x8 v = *reinterpret_cast<const bf16x8*>(qrow + kk * 32 + g4 * 8);
+      bf16x8 v = *reinterpret_cast<const bf16x8*>(qrow + KV::q_dim(kk, g4));
       qf[kk] = row_ok ? v : bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
     }
   }
@@ -178,26 +371,13 @@ __global__ void __launch_bounds__(256) paged_attn_kernel(
   const int pp_begin = p_begin >> 5;
   const int pp_end = (p_end + 31) >> 5;
   const int n_pages = (p_end + kBS - 1) / kBS;
-  const size_t page_stride = (size_t)Hkv * kBS * kD;
+  const size_t page_stride = (size_t)Hkv * kBS * kD;  // cache elements (bf16) or bytes (fp8)
 
   // (a generic pointer's low 32 bits are the LDS offset)
   const uint32_t vimg = (uint32_t)(uintptr_t)&sm_o[0][0][0] + wid * 8448u;
   // clamp: a corrupt block table must not become an out-of-bounds fault
   auto page_a = [&](int pp) { return min(max(bt[2 * pp], 0), num_blocks - 1); };
   auto page_b = [&](int pp, int pa) { return (2 * pp + 1 < n_pages) ? min(max(bt[2 * pp + 1], 0), num_blocks - 1) : pa; };
-  // the pair's 32 token rows of this kv head by LDS-DMA into this wave's V image
-  auto issue_v = [&](int pa, int pb) {
-    const uint16_t* vA = vc + pa * page_stride + (size_t)kvh * kBS * kD;
-    const uint16_t* vB = vc + pb * page_stride + (size_t)kvh * kBS * kD;
-    const uint32_t dst = vimg;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int trow = (4 * i + g4) & 15;
-      const uint16_t* src = (i < 4 ? vA : vB) + trow * kD + ((r ^ vswz(trow)) << 3);
-      __builtin_amdgcn_global_load_lds((const void*)src, (lds_void_t*)(uintptr_t)(dst + 1024u * i), 16, 0,
-                                       (NT & 1) ? 2 /* nt */ : 0);
-    }
-  };
   // page ids one pair ahead: the block-table loads of pair pp + 4 run under pair pp
   int pgA = 0, pgB = 0;
   if (pp_begin + wid < pp_end) {
@@ -205,38 +385,30 @@ __global__ void __launch_bounds__(256) paged_attn_kernel(
     pgB = (bt0 + 1 < n_pages) ? min(max(rawB, 0), num_blocks - 1) : pgA;
   }
   for (int pp = pp_begin + wid; pp < pp_end; pp += 4) {
-    const uint16_t* kA = kc + pgA * page_stride + (size_t)kvh * kBS * kD;
-    const uint16_t* kB = kc + pgB * page_stride + (size_t)kvh * kBS * kD;
-
-    // K rows of MFMA row r: pair tokens 8*(r>>2) + (r&3) (first S MFMA) and +4 (second)
-    const uint16_t* kR = (r >> 3 ? kB : kA) + (8 * ((r >> 2) & 1) + (r & 3)) * kD;
+    // memory operations in this order: the pair's K, its V behind them, the next pair's page ids
+    typename KV::Pair pr;
     bf16x8 ka[4], kb[4];
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) {
-      if constexpr ((NT & 1) != 0) {
-        ka[kk] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(kR + kk * 32 + g4 * 8));
-        kb[kk] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(kR + 4 * kD + kk * 32 + g4 * 8));
-      } else {
-        ka[kk] = *reinterpret_cast<const bf16x8*>(kR + kk * 32 + g4 * 8);
-        kb[kk] = *reinterpret_cast<const bf16x8*>(kR + 4 * kD + kk * 32 + g4 * 8);
-      }
-    }
-    // this pair's V image, issued behind the K loads (the S MFMAs wait for those only; the
-    // previous pair's transposed reads are complete: their MFMAs consumed them)
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    issue_v(pgA, pgB);
+    kv.template load_k<NT>(pr, pgA, pgB, page_stride, kvh, lane, ka, kb);
+    kv.template issue_v<NT>(pr, pgA, pgB, page_stride, kvh, lane, vimg);
     if (pp + 4 < pp_end) {
       pgA = page_a(pp + 4);
       pgB = page_b(pp + 4, pgA);
     }
     bf16x8 vf8[8];
-    // S^T[token][row]: lane holds row r, tokens 4*g4 + i of each page
+    // S^T[token][row]: lane holds row r, tokens 8*g4 + i (sa) and 8*g4 + 4 + i (sb) of the pair
     f32x4 sa = {0.f, 0.f, 0.f, 0.f}, sb = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk) {
       sa = mfma16(ka[kk], qf[kk], sa);
       sb = mfma16(kb[kk], qf[kk], sb);
     }
+    // S *= 2^e_k first (exact; scaled formats only), then the softmax scale.  The score is read
+    // inside each select, not into temporaries ahead of the masks: that is the order the compiler
+    // schedules the S MFMAs and the mask by (profiles/attention_one_kernel.md, section 1)
+    auto s_of = [&](const f32x4& s, int h, int i) {
+      if constexpr (KV::kScaled) return s[i] * KV::k_scale(pr, h, i);
+      else return s[i];
+    };
     const int tokA = pp * 32 + g4 * 8, tokB = tokA + 4;
     float pa[4], pb[4];
     float mx = kNegBig;
@@ -244,11 +416,11 @@ __global__ void __launch_bounds__(256) paged_attn_kernel(
     for (int i = 0; i < 4; ++i) {
       const int ta = tokA + i, tb = tokB + i;
       if constexpr (WIN) {
-        pa[i] = (ta < p_end && ta <= pos_r && ta > pos_r - window) ? sa[i] * scale_log2 : -INFINITY;
-        pb[i] = (tb < p_end && tb <= pos_r && tb > pos_r - window) ? sb[i] * scale_log2 : -INFINITY;
+        pa[i] = (ta < p_end && ta <= pos_r && ta > pos_r - window) ? s_of(sa, 0, i) * scale_log2 : -INFINITY;
+        pb[i] = (tb < p_end && tb <= pos_r && tb > pos_r - window) ? s_of(sb, 1, i) * scale_log2 : -INFINITY;
       } else {
-        pa[i] = (ta < p_end && ta <= pos_r) ? sa[i] * scale_log2 : -INFINITY;
-        pb[i] = (tb < p_end && tb <= pos_r) ? sb[i] * scale_log2 : -INFINITY;
+        pa[i] = (ta < p_end && ta <= pos_r) ? s_of(sa, 0, i) * scale_log2 : -INFINITY;
+        pb[i] = (tb < p_end && tb <= pos_r) ? s_of(sb, 1, i) * scale_log2 : -INFINITY;
       }
       mx = fmaxf(mx, fmaxf(pa[i], pb[i]));
     }
@@ -263,19 +435,25 @@ __global__ void __launch_bounds__(256) paged_attn_kernel(
       pb[i] = fast_exp2(pb[i] - m_new);
       rs += pa[i] + pb[i];
     }
-    l = l * alpha + rs;
+    l = l * alpha + rs;  // the unscaled p
     bf16x8 pf;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      pf[i] = (short)f2bf(pa[i]);
-      pf[4 + i] = (short)f2bf(pb[i]);
+      if constexpr (KV::kScaled) {  // p 2^e_v: exact before the rounding
+        pf[i] = (short)f2bf(pa[i] * KV::v_scale(pr, 0, i));
+        pf[4 + i] = (short)f2bf(pb[i] * KV::v_scale(pr, 1, i));
+      } else {
+        pf[i] = (short)f2bf(pa[i]);
+        pf[4 + i] = (short)f2bf(pb[i]);
+      }
     }
     {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's V image has landed
+      kv.v_ready(pr, lane, vimg);
       uint32_t b0 = vimg + vt_base(lane);
       asm volatile("" : "+v"(b0));  // no hoisting of the 16 read addresses out of the loop
 #pragma unroll
       for (int d = 0; d < 8; ++d) vf8[d] = vt_frag(b0, d);
+      kv.v_read_done();
     }
 #pragma unroll
     for (int d = 0; d < 8; ++d) {
@@ -367,24 +545,8 @@ __global__ void __launch_bounds__(256) paged_attn_kernel(
   }
   __syncthreads();
   if (!row_valid) return;
-  const size_t base = ((size_t)tile * Hkv + kvh) * nparts;
-  float MM = kNegBig;
-  for (int p = 0; p < nvalid; ++p) MM = fmaxf(MM, part_ml[((base + p) * 16 + rr) * 2]);
-  float LL = 0.f, a2[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  for (int p = 0; p < nvalid; ++p) {
-    const size_t pb = (base + p) * 16 + rr;
-    const float f = exp2f(part_ml[pb * 2] - MM);
-    LL += f * part_ml[pb * 2 + 1];
-    const float4* po = reinterpret_cast<const float4*>(part_o + pb * kD + c);
-    const float4 x0 = po[0], x1 = po[1];
-    a2[0] += f * x0.x; a2[1] += f * x0.y; a2[2] += f * x0.z; a2[3] += f * x0.w;
-    a2[4] += f * x1.x; a2[5] += f * x1.y; a2[6] += f * x1.z; a2[7] += f * x1.w;
-  }
-  const float inv = LL > 0.f ? 1.f / LL : 0.f;
-  u32x4 ov;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) ov[j] = pack2(a2[2 * j] * inv, a2[2 * j + 1] * inv);
-  *reinterpret_cast<u32x4*>(out + ((size_t)(qs + qi2) * Hq + head2) * kD + c) = ov;
+  combine_slabs(out + ((size_t)(qs + qi2) * Hq + head2) * kD + c, part_o, part_ml,
+                ((size_t)tile * Hkv + kvh) * nparts, nvalid, rr, c);
 }
 
 template <int G, bool WIN = false>
@@ -405,25 +567,9 @@ __global__ void __launch_bounds__(256) attn_reduce_kernel(
   const int rr = threadIdx.x >> 4, c = (threadIdx.x & 15) * 8;
   const int qi = q0 + rr / G;
   if (qi >= ql) return;
-  const size_t base = ((size_t)tile * Hkv + kvh) * nparts;
-  float M = kNegBig;
-  for (int p = 0; p < nvalid; ++p) M = fmaxf(M, part_ml[((base + p) * 16 + rr) * 2]);
-  float L = 0.f, acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  for (int p = 0; p < nvalid; ++p) {
-    const size_t pb = (base + p) * 16 + rr;
-    const float f = exp2f(part_ml[pb * 2] - M);
-    L += f * part_ml[pb * 2 + 1];
-    const float4* po = reinterpret_cast<const float4*>(part_o + pb * kD + c);
-    float4 a = po[0], b = po[1];
-    acc[0] += f * a.x; acc[1] += f * a.y; acc[2] += f * a.z; acc[3] += f * a.w;
-    acc[4] += f * b.x; acc[5] += f * b.y; acc[6] += f * b.z; acc[7] += f * b.w;
-  }
-  const float inv = L > 0.f ? 1.f / L : 0.f;
-  u32x4 ov;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) ov[j] = pack2(acc[2 * j] * inv, acc[2 * j + 1] * inv);
   const int head = kvh * G + (rr % G);
-  *reinterpret_cast<u32x4*>(out + ((size_t)(qs + qi) * Hq + head) * kD + c) = ov;
+  combine_slabs(out + ((size_t)(qs + qi) * Hq + head) * kD + c, part_o, part_ml,
+                ((size_t)tile * Hkv + kvh) * nparts, nvalid, rr, c);
 }
 
 // K / V pages of the decode kernel non-temporal (read once per step by one workgroup; the
@@ -435,46 +581,46 @@ int attn_kv_nt(int set) {
   return g_attn_kv_nt;
 }
 
-template <int G>
-static void launch_g(void* out, float* part_o, float* part_ml, const void* q, const void* kc,
-                     const void* vc, const int* bt, int bt_stride, const int* tile_seq,
-                     const int* tile_q0, const int* q_start, const int* q_len, const int* ctx_len,
-                     int num_tiles, int Hq, int Hkv, float scale_log2, int part_tokens, int nparts,
-                     int num_blocks, int* sem, int window, hipStream_t st) {
-  dim3 grid(num_tiles, Hkv, nparts);
+// the decode launch of either KV format: picks the GQA group and the NT instantiation, and runs
+// the split-KV combine as a second launch when there are no tickets (sem == nullptr; the
+// partials are fp32 whatever the KV format)
+template <class KV>
+static void launch_decode(KV kv, void* out, float* part_o, float* part_ml, const void* q, const int* bt,
+                          int bt_stride, const int* tile_seq, const int* tile_q0, const int* q_start,
+                          const int* q_len, const int* ctx_len, int num_tiles, int Hq, int Hkv,
+                          float scale_log2, int part_tokens, int nparts, int num_blocks, int* sem, int window,
+                          hipStream_t st) {
+  if (num_tiles == 0) return;
   // K / V pages non-temporal (attn_kv_nt op): each is read once per step by one workgroup
   // (below 8 query tiles the default policy: batch 4 lost 0.7 % with it, batch 16 gained 1.8 %)
   const int nt = num_tiles >= 8 ? g_attn_kv_nt : 0;
-  auto kern = nt == 3 ? paged_attn_kernel<G, 3> : nt ? paged_attn_kernel<G, 1> : paged_attn_kernel<G, 0>;
-  if (window > 0)  // the windowed instantiations; window 0 runs exactly the kernels above
-    kern = nt == 3 ? paged_attn_kernel<G, 3, true> : nt ? paged_attn_kernel<G, 1, true> : paged_attn_kernel<G, 0, true>;
-  kern<<<grid, 256, 0, st>>>((uint16_t*)out, part_o, part_ml, (const uint16_t*)q, (const uint16_t*)kc,
-                             (const uint16_t*)vc, bt, bt_stride, tile_seq, tile_q0, q_start, q_len, ctx_len,
-                             Hq, Hkv, scale_log2, part_tokens, nparts, num_blocks, sem, window);
-  if (nparts > 1 && sem == nullptr) {
-    auto red = window > 0 ? attn_reduce_kernel<G, true> : attn_reduce_kernel<G, false>;
-    red<<<dim3(num_tiles, Hkv), 256, 0, st>>>(
-        (uint16_t*)out, part_o, part_ml, tile_seq, tile_q0, q_start, q_len, ctx_len, Hq, Hkv,
-        part_tokens, nparts, window);
-  }
-}
-
-// the split-KV combine as a launch of its own, for attention_fp8.hip: the partials are fp32
-// whatever the KV dtype, so the fp8 kernel ends in the same (unwindowed) reduce
-void launch_attn_reduce(void* out, const float* part_o, const float* part_ml, const int* tile_seq,
-                        const int* tile_q0, const int* q_start, const int* q_len, const int* ctx_len,
-                        int num_tiles, int Hq, int Hkv, int part_tokens, int nparts, hipStream_t st) {
-  auto red = attn_reduce_kernel<1, false>;
+  auto go = [&](auto g_tag) {
+    constexpr int G = decltype(g_tag)::value;
+    auto kern = nt == 3 ? paged_attn_kernel<G, 3, false, KV> : nt ? paged_attn_kernel<G, 1, false, KV>
+                                                                  : paged_attn_kernel<G, 0, false, KV>;
+    // the windowed instantiations (bf16 pages only); window 0 runs exactly the kernels above
+    if constexpr (std::is_same_v<KV, KvBf16>)
+      if (window > 0)
+        kern = nt == 3 ? paged_attn_kernel<G, 3, true, KV> : nt ? paged_attn_kernel<G, 1, true, KV>
+                                                                : paged_attn_kernel<G, 0, true, KV>;
+    kern<<<dim3(num_tiles, Hkv, nparts), 256, 0, st>>>(
+        (uint16_t*)out, part_o, part_ml, (const uint16_t*)q, kv, bt, bt_stride, tile_seq, tile_q0, q_start,
+        q_len, ctx_len, Hq, Hkv, scale_log2, part_tokens, nparts, num_blocks, sem, window);
+    if (nparts > 1 && sem == nullptr) {
+      auto red = window > 0 ? attn_reduce_kernel<G, true> : attn_reduce_kernel<G, false>;
+      red<<<dim3(num_tiles, Hkv), 256, 0, st>>>(
+          (uint16_t*)out, part_o, part_ml, tile_seq, tile_q0, q_start, q_len, ctx_len, Hq, Hkv,
+          part_tokens, nparts, window);
+    }
+  };
   switch (Hq / Hkv) {
-    case 1: break;
-    case 2: red = attn_reduce_kernel<2, false>; break;
-    case 4: red = attn_reduce_kernel<4, false>; break;
-    case 8: red = attn_reduce_kernel<8, false>; break;
-    case 16: red = attn_reduce_kernel<16, false>; break;
-    default: return;
+    case 1: go(std::integral_constant<int, 1>{}); break;
+    case 2: go(std::integral_constant<int, 2>{}); break;
+    case 4: go(std::integral_constant<int, 4>{}); break;
+    case 8: go(std::integral_constant<int, 8>{}); break;
+    case 16: go(std::integral_constant<int, 16>{}); break;
+    default: break;
   }
-  red<<<dim3(num_tiles, Hkv), 256, 0, st>>>((uint16_t*)out, part_o, part_ml, tile_seq, tile_q0, q_start, q_len,
-                                            ctx_len, Hq, Hkv, part_tokens, nparts, 0);
 }
 
 void launch_paged_attention(void* out, float* part_o, float* part_ml, const void* q,
@@ -483,22 +629,20 @@ void launch_paged_attention(void* out, float* part_o, float* part_ml, const void
                             const int* q_len, const int* ctx_len, int num_tiles, int Hq, int Hkv,
                             float scale_log2, int part_tokens, int nparts, int num_blocks,
                             int* sem, int window, hipStream_t st) {
-  if (num_tiles == 0) return;
-  const int G = Hq / Hkv;
-#define MLOP_ATTN_CASE(GG)                                                                        \
-  case GG:                                                                                        \
-    launch_g<GG>(out, part_o, part_ml, q, kc, vc, bt, bt_stride, tile_seq, tile_q0, q_start,     \
-                 q_len, ctx_len, num_tiles, Hq, Hkv, scale_log2, part_tokens, nparts, num_blocks, sem, window, st); \
-    break;
-  switch (G) {
-    MLOP_ATTN_CASE(1)
-    MLOP_ATTN_CASE(2)
-    MLOP_ATTN_CASE(4)
-    MLOP_ATTN_CASE(8)
-    MLOP_ATTN_CASE(16)
-    default: break;
-  }
-#undef MLOP_ATTN_CASE
+  launch_decode(KvBf16{(const uint16_t*)kc, (const uint16_t*)vc}, out, part_o, part_ml, q, bt, bt_stride,
+                tile_seq, tile_q0, q_start, q_len, ctx_len, num_tiles, Hq, Hkv, scale_log2, part_tokens, nparts,
+                num_blocks, sem, window, st);
+}
+
+void launch_paged_attention_fp8(void* out, float* part_o, float* part_ml, const void* q, const void* kc,
+                                const void* vc, const void* ks, const void* vs, const int* bt,
+                                int bt_stride, const int* tile_seq, const int* tile_q0, const int* q_start,
+                                const int* q_len, const int* ctx_len, int num_tiles, int Hq, int Hkv,
+                                float scale_log2, int part_tokens, int nparts, int num_blocks, int* sem,
+                                hipStream_t st) {
+  launch_decode(KvFp8{(const uint8_t*)kc, (const uint8_t*)vc, (const uint8_t*)ks, (const uint8_t*)vs, Hkv * kBS},
+                out, part_o, part_ml, q, bt, bt_stride, tile_seq, tile_q0, q_start, q_len, ctx_len, num_tiles,
+                Hq, Hkv, scale_log2, part_tokens, nparts, num_blocks, sem, 0, st);
 }
 
 // ---------------------------------------------------------------------------

@@ -194,38 +194,48 @@ int64_t attn_fused_max_pairs(int64_t n) {
   return prev;
 }
 
-void paged_attention(Tensor out, Tensor part_o, Tensor part_ml, Tensor part_sem, Tensor q, Tensor k_cache,
-                     Tensor v_cache, Tensor block_tables, Tensor tile_seq, Tensor tile_q0,
-                     Tensor q_start, Tensor q_len, Tensor ctx_len, double scale,
-                     int64_t part_tokens, int64_t nparts, int64_t window) {
-  TORCH_CHECK(window >= 0 && window < (1 << 30), "window must be >= 0 (0: no sliding window)");
-  check_bf16(out, "out"); check_bf16(q, "q"); check_bf16(k_cache, "k_cache");
-  check_bf16(v_cache, "v_cache");
+// The arguments the decode attention ops share, whatever the KV format (k_cache: checked by the
+// caller as [NB, Hkv, 16, 128] of its format), and what both launches derive from them: the
+// partial buffers (nullptr with one partition) and the ticket buffer of the in-launch split-KV
+// combine (nullptr: the combine runs as a second launch).
+struct DecodeAttention {
+  int Hq, Hkv, num_tiles;
+  float* part_o;
+  float* part_ml;
+  int* sem;
+};
+static DecodeAttention check_decode_attention(const Tensor& out, const Tensor& part_o, const Tensor& part_ml,
+                                              const Tensor& part_sem, const Tensor& q, const Tensor& k_cache,
+                                              const Tensor& block_tables, const Tensor& tile_seq, const Tensor& tile_q0,
+                                              const Tensor& q_start, const Tensor& q_len, const Tensor& ctx_len,
+                                              int64_t part_tokens, int64_t nparts) {
+  check_bf16(out, "out"); check_bf16(q, "q");
   check_i32(block_tables, "block_tables"); check_i32(tile_seq, "tile_seq");
   check_i32(tile_q0, "tile_q0"); check_i32(q_start, "q_start"); check_i32(q_len, "q_len");
   check_i32(ctx_len, "ctx_len");
   TORCH_CHECK(q.dim() == 3 && q.size(2) == 128, "q must be [T, Hq, 128]");
-  TORCH_CHECK(k_cache.dim() == 4 && k_cache.size(2) == 16 && k_cache.size(3) == 128,
-              "k_cache must be [NB, Hkv, 16, 128]");
-  TORCH_CHECK(v_cache.sizes() == at::IntArrayRef({k_cache.size(0), k_cache.size(1), 16, 128}),
-              "v_cache must be [NB, Hkv, 16, 128] (token-major, as k_cache)");
   const int Hq = (int)q.size(1), Hkv = (int)k_cache.size(1);
   TORCH_CHECK(Hq % Hkv == 0, "Hq % Hkv");
   const int G = Hq / Hkv;
   TORCH_CHECK(G == 1 || G == 2 || G == 4 || G == 8 || G == 16, "GQA group must divide 16");
   TORCH_CHECK(out.sizes() == q.sizes(), "out shape");
   TORCH_CHECK(tile_seq.numel() == tile_q0.numel(), "tile arrays");
+  // (the kernel reads bt[min(.., stride - 1)] ahead of the lengths)
+  TORCH_CHECK(block_tables.dim() == 2 && block_tables.size(1) >= 1, "block_tables must be [rows, pages]");
   TORCH_CHECK(q_start.numel() == q_len.numel() && q_len.numel() == ctx_len.numel() &&
                   block_tables.size(0) >= q_len.numel(),
               "per-sequence arrays");
   TORCH_CHECK(part_tokens % 32 == 0 && part_tokens > 0 && nparts >= 1, "partition size");
-  const int num_tiles = (int)tile_seq.numel();
+  const int64_t num_tiles = tile_seq.numel();
+  DecodeAttention a{Hq, Hkv, (int)num_tiles, nullptr, nullptr, nullptr};
   if (nparts > 1) {
     TORCH_CHECK(part_o.scalar_type() == at::kFloat && part_ml.scalar_type() == at::kFloat,
                 "partials f32");
-    TORCH_CHECK(part_o.numel() >= (int64_t)num_tiles * Hkv * nparts * 16 * 128 &&
-                    part_ml.numel() >= (int64_t)num_tiles * Hkv * nparts * 16 * 2,
+    TORCH_CHECK(part_o.numel() >= num_tiles * Hkv * nparts * 16 * 128 &&
+                    part_ml.numel() >= num_tiles * Hkv * nparts * 16 * 2,
                 "partial workspace too small");
+    a.part_o = part_o.data_ptr<float>();
+    a.part_ml = part_ml.data_ptr<float>();
   }
   // part_sem: zero-initialised int32 tickets, one per (tile, kv head), re-armed by the
   // kernel; empty -> the split-KV combine runs as a second launch
@@ -233,25 +243,37 @@ void paged_attention(Tensor out, Tensor part_o, Tensor part_ml, Tensor part_sem,
   // saved launch above that (batch 8: 1800 -> 1783 tok/s, scripts/run52.sh).  With the
   // partials stored sc1 and no producer fence it wins at every batch measured (batch 8 / 16
   // / 64: +0.7 / +0.7 / +0.2 %, scripts/history/r4_fusedc.sh), so the cap is off by default.
-  const int max_pairs = attn_fused_pairs_cap();
-  int* sem = nullptr;
-  if (nparts > 1 && part_sem.numel() > 0 && num_tiles * Hkv <= max_pairs) {
+  if (nparts > 1 && part_sem.numel() > 0 && num_tiles * Hkv <= attn_fused_pairs_cap()) {
     check_i32(part_sem, "part_sem");
-    TORCH_CHECK(part_sem.numel() >= (int64_t)num_tiles * Hkv, "part_sem too small");
-    sem = part_sem.data_ptr<int>();
+    TORCH_CHECK(part_sem.numel() >= num_tiles * Hkv, "part_sem too small");
+    a.sem = part_sem.data_ptr<int>();
   }
+  return a;
+}
+
+void paged_attention(Tensor out, Tensor part_o, Tensor part_ml, Tensor part_sem, Tensor q, Tensor k_cache,
+                     Tensor v_cache, Tensor block_tables, Tensor tile_seq, Tensor tile_q0,
+                     Tensor q_start, Tensor q_len, Tensor ctx_len, double scale,
+                     int64_t part_tokens, int64_t nparts, int64_t window) {
+  TORCH_CHECK(window >= 0 && window < (1 << 30), "window must be >= 0 (0: no sliding window)");
+  check_bf16(k_cache, "k_cache"); check_bf16(v_cache, "v_cache");
+  TORCH_CHECK(k_cache.dim() == 4 && k_cache.size(2) == 16 && k_cache.size(3) == 128,
+              "k_cache must be [NB, Hkv, 16, 128]");
+  TORCH_CHECK(v_cache.sizes() == at::IntArrayRef({k_cache.size(0), k_cache.size(1), 16, 128}),
+              "v_cache must be [NB, Hkv, 16, 128] (token-major, as k_cache)");
+  const DecodeAttention a = check_decode_attention(out, part_o, part_ml, part_sem, q, k_cache, block_tables, tile_seq,
+                                                   tile_q0, q_start, q_len, ctx_len, part_tokens, nparts);
   c10::DeviceGuard g(q.device());
   const float scale_log2 = (float)(scale * 1.4426950408889634);
   mlop::launch_paged_attention(
-      out.data_ptr(), nparts > 1 ? part_o.data_ptr<float>() : nullptr,
-      nparts > 1 ? part_ml.data_ptr<float>() : nullptr, q.data_ptr(), k_cache.data_ptr(),
-      v_cache.data_ptr(), block_tables.data_ptr<int>(), (int)block_tables.stride(0),
-      tile_seq.data_ptr<int>(), tile_q0.data_ptr<int>(), q_start.data_ptr<int>(),
-      q_len.data_ptr<int>(), ctx_len.data_ptr<int>(), num_tiles, Hq, Hkv, scale_log2,
-      (int)part_tokens, (int)nparts, (int)k_cache.size(0), sem, (int)window, cur_stream());
+      out.data_ptr(), a.part_o, a.part_ml, q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
+      block_tables.data_ptr<int>(), (int)block_tables.stride(0), tile_seq.data_ptr<int>(),
+      tile_q0.data_ptr<int>(), q_start.data_ptr<int>(), q_len.data_ptr<int>(), ctx_len.data_ptr<int>(),
+      a.num_tiles, a.Hq, a.Hkv, scale_log2, (int)part_tokens, (int)nparts, (int)k_cache.size(0), a.sem,
+      (int)window, cur_stream());
 }
 
-// ---- fp8 KV cache (kv_fp8.hip, attention_fp8.hip): e4m3fn pages + one scale byte per row
+// ---- fp8 KV cache (kv_fp8.hip, attention.hip's KvFp8): e4m3fn pages + one scale byte per row
 void check_fp8_cache(const Tensor& c, const Tensor& sc, const char* name) {
   TORCH_CHECK(c.is_cuda() && c.scalar_type() == at::kFloat8_e4m3fn && c.is_contiguous(), name,
               " must be a contiguous float8_e4m3fn GPU tensor");
@@ -292,47 +314,18 @@ void paged_attention_fp8(Tensor out, Tensor part_o, Tensor part_ml, Tensor part_
                          Tensor v_cache, Tensor k_scale, Tensor v_scale, Tensor block_tables, Tensor tile_seq,
                          Tensor tile_q0, Tensor q_start, Tensor q_len, Tensor ctx_len, double scale,
                          int64_t part_tokens, int64_t nparts) {
-  check_bf16(out, "out"); check_bf16(q, "q");
   check_fp8_cache(k_cache, k_scale, "k_cache"); check_fp8_cache(v_cache, v_scale, "v_cache");
-  check_i32(block_tables, "block_tables"); check_i32(tile_seq, "tile_seq");
-  check_i32(tile_q0, "tile_q0"); check_i32(q_start, "q_start"); check_i32(q_len, "q_len");
-  check_i32(ctx_len, "ctx_len");
-  TORCH_CHECK(q.dim() == 3 && q.size(2) == 128, "q must be [T, Hq, 128]");
   TORCH_CHECK(v_cache.sizes() == k_cache.sizes(), "k and v caches differ in shape");
-  const int Hq = (int)q.size(1), Hkv = (int)k_cache.size(1);
-  TORCH_CHECK(Hq % Hkv == 0, "Hq % Hkv");
-  const int G = Hq / Hkv;
-  TORCH_CHECK(G == 1 || G == 2 || G == 4 || G == 8 || G == 16, "GQA group must divide 16");
-  TORCH_CHECK(out.sizes() == q.sizes(), "out shape");
-  TORCH_CHECK(tile_seq.numel() == tile_q0.numel(), "tile arrays");
-  TORCH_CHECK(block_tables.dim() == 2 && block_tables.size(1) >= 1, "block_tables must be [rows, pages]");
-  TORCH_CHECK(q_start.numel() == q_len.numel() && q_len.numel() == ctx_len.numel() &&
-                  block_tables.size(0) >= q_len.numel(),
-              "per-sequence arrays");
-  TORCH_CHECK(part_tokens % 32 == 0 && part_tokens > 0 && nparts >= 1, "partition size");
-  const int num_tiles = (int)tile_seq.numel();
-  if (nparts > 1) {
-    TORCH_CHECK(part_o.scalar_type() == at::kFloat && part_ml.scalar_type() == at::kFloat, "partials f32");
-    TORCH_CHECK(part_o.numel() >= (int64_t)num_tiles * Hkv * nparts * 16 * 128 &&
-                    part_ml.numel() >= (int64_t)num_tiles * Hkv * nparts * 16 * 2,
-                "partial workspace too small");
-  }
-  // part_sem as paged_attention: zeroed tickets -> in-launch combine, empty -> reduce launch
-  int* sem = nullptr;
-  if (nparts > 1 && part_sem.numel() > 0 && num_tiles * Hkv <= attn_fused_pairs_cap()) {
-    check_i32(part_sem, "part_sem");
-    TORCH_CHECK(part_sem.numel() >= (int64_t)num_tiles * Hkv, "part_sem too small");
-    sem = part_sem.data_ptr<int>();
-  }
+  const DecodeAttention a = check_decode_attention(out, part_o, part_ml, part_sem, q, k_cache, block_tables, tile_seq,
+                                                   tile_q0, q_start, q_len, ctx_len, part_tokens, nparts);
   c10::DeviceGuard g(q.device());
   const float scale_log2 = (float)(scale * 1.4426950408889634);
   mlop::launch_paged_attention_fp8(
-      out.data_ptr(), nparts > 1 ? part_o.data_ptr<float>() : nullptr,
-      nparts > 1 ? part_ml.data_ptr<float>() : nullptr, q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
+      out.data_ptr(), a.part_o, a.part_ml, q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
       k_scale.data_ptr(), v_scale.data_ptr(), block_tables.data_ptr<int>(), (int)block_tables.stride(0),
       tile_seq.data_ptr<int>(), tile_q0.data_ptr<int>(), q_start.data_ptr<int>(), q_len.data_ptr<int>(),
-      ctx_len.data_ptr<int>(), num_tiles, Hq, Hkv, scale_log2, (int)part_tokens, (int)nparts,
-      (int)k_cache.size(0), sem, cur_stream());
+      ctx_len.data_ptr<int>(), a.num_tiles, a.Hq, a.Hkv, scale_log2, (int)part_tokens, (int)nparts,
+      (int)k_cache.size(0), a.sem, cur_stream());
 }
 
 // ---- lazily backed KV arenas (vmm.hip)

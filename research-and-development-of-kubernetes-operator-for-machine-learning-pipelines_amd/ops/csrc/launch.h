@@ -33,12 +33,8 @@ void launch_paged_attention(void* out, float* part_o, float* part_ml, const void
                             const int* q_len, const int* ctx_len, int num_tiles, int Hq, int Hkv,
                             float scale_log2, int part_tokens, int nparts, int num_blocks,
                             int* sem, int window, hipStream_t st);  // window 0: causal only
-// attention.hip's split-KV reduce on its own (fp32 partials; the fp8 kernel's second launch)
-void launch_attn_reduce(void* out, const float* part_o, const float* part_ml, const int* tile_seq,
-                        const int* tile_q0, const int* q_start, const int* q_len, const int* ctx_len,
-                        int num_tiles, int Hq, int Hkv, int part_tokens, int nparts, hipStream_t st);
 // fp8 KV cache (e4m3fn pages [NB, Hkv, 16, 128] + one power-of-two scale byte per row,
-// [NB, Hkv, 16]): kv_fp8.hip's RoPE + cache writer and attention_fp8.hip's decode attention
+// [NB, Hkv, 16]): kv_fp8.hip's RoPE + cache writer and attention.hip's decode kernel over KvFp8
 void launch_rope_cache_fp8(void* q_out, void* k_cache, void* v_cache, void* k_scale, void* v_scale,
                            const void* qkv, const int* pos, const float* cos_sin, const int* slots, int T,
                            int Hq, int Hkv, int qkv_stride, int BS, hipStream_t st);

@@ -1,5 +1,5 @@
 """The serving engine with kv_cache_dtype="fp8" on the GPU (kv_fp8.hip's writer and
-attention_fp8.hip's attention under chunked prefill, eager and hipGraph decode, prefix caching,
+attention.hip's KvFp8 decode kernel under chunked prefill, eager and hipGraph decode, prefix caching,
 LoRA) against the dense fp32 oracle that fake-quantises post-RoPE K and V with the cache's rule."""
 import pytest
 import torch

@@ -1,5 +1,5 @@
-"""The fp8 KV cache kernels: kv_fp8.hip's RoPE + cache writer and attention_fp8.hip's paged
-attention over e4m3fn pages with one power-of-two scale byte per (token, kv head) row.
+"""The fp8 KV cache kernels: kv_fp8.hip's RoPE + cache writer and attention.hip's decode
+kernel (KvFp8) over e4m3fn pages with one power-of-two scale byte per (token, kv head) row.
 
 Writer: the scale bytes are the reference rule (ops/reference.py) applied to an fp32 RoPE
 reference, the stored rows are within half an e4m3 ulp (+ half the subnormal spacing, + the
@@ -215,6 +215,18 @@ def test_nt_policies_bit_identical(gpu, attn_fused_all, form):
     finally:
         torch.ops.mlop.attn_kv_nt(prev)
     assert all(torch.equal(outs[0].view(torch.int16), o.view(torch.int16)) for o in outs[1:])
+
+
+def test_fused_and_reduce_combine_bit_identical(gpu, attn_fused_all):
+    """The in-launch combine and the reduce launch are one function over the same slabs in the
+    same order: written_case's launch (contexts 1 .. 300, three partitions of 128, G = 4) gives
+    the same bytes either way.  (bf16 and windowed bf16: test_probes_attention_gpu.py.)"""
+    m, q, caches, _ = written_case(str(gpu), 4)
+    outs = {}
+    for form in ("reduce3", "fused3"):
+        outs[form] = run_fp8(ap.repartition(m, *FORMS[form][:2], sem=FORMS[form][2]), q, caches)
+        assert torch.isfinite(outs[form]).all()
+    assert torch.equal(outs["reduce3"].view(torch.int16), outs["fused3"].view(torch.int16))
 
 
 # ------------------------------------------------------------------ probes --

@@ -85,6 +85,36 @@ def test_windowed_decode(gpu, attn_fused_all, W, G, form):
         run_forms(m, q, kc, vc, exp, part_tokens, nparts, fused, f"{kind}/{schedule}")
 
 
+@functools.lru_cache(maxsize=1)
+def randn_case(device, G=4, seed=0):
+    """Decode rows at every page / pair edge up to 300 keys, 5-token rows, a chunk that straddles
+    tiles and one padding row, over randn q / K / V: partials whose every bit matters."""
+    ctxs = [1, 15, 16, 17, 31, 32, 33, 127, 129, 300]
+    q_lens, ctx_lens = [1] * len(ctxs) + [5, 5, 16 // G + 1, 1], ctxs + [35, 300, 260, 0]
+    m = ap.make_layout(q_lens, ctx_lens, ap.HKV, G, device=device, seed=seed)
+    g = torch.Generator().manual_seed(seed)
+    kc, vc = (torch.randn(m.NB, ap.HKV, 16, 128, generator=g).to(torch.bfloat16).to(device) for _ in range(2))
+    q = torch.randn(m.num_tokens, ap.HKV * G, 128, generator=g).to(torch.bfloat16).to(device)
+    return m, q, kc, vc
+
+
+@pytest.mark.parametrize("W", [0, 100, 300])
+def test_fused_and_reduce_combine_bit_identical(gpu, attn_fused_all, W):
+    """The in-launch combine and the reduce launch are one function over the same slabs in the
+    same order, so three partitions of 128 keys (G = 4) give the same bytes either way: plain, and
+    under windows that leave a row two (100) and three (300) partitions counted from its start.
+    (fp8 pages: test_fp8_kv_kernels_gpu.py.)"""
+    m, q, kc, vc = randn_case(str(gpu))
+    outs = []
+    for fused in (False, True):
+        mm = ap.repartition(m, 128, 3, sem=fused)
+        mm.window = W
+        outs.append(ops.paged_attention(q, kc, vc, mm, out=torch.full_like(q, float("nan"))))
+        assert torch.isfinite(outs[-1]).all()
+    assert float(outs[0].float().abs().max()) > 0
+    assert torch.equal(outs[0].view(torch.int16), outs[1].view(torch.int16))
+
+
 FLASH_GRIDS = dict(grid=(0, 0), persist3=(3 * 64, 0), stream3=(3 * 64, 1), stream1=(64, 1))
 
 
