@@ -266,6 +266,31 @@ class _AllGreedy:
 _ALL_GREEDY = _AllGreedy()
 
 
+class _Step:
+    """One step as ``Engine._build_step`` planned it and ``Engine._issue`` launches it.  The decode
+    part: engine ``rows`` (int32 [B]) and their context lengths ``ctx_d``.  The prompt part (all
+    empty in a decode step): the sequences of ``batch`` with their ``chunks`` (tokens this step),
+    ``p_ctx`` (cached length after it), ``done`` (the prompt completes) and ``done_seqs``.  The
+    logits rows are the decode rows, then ``done_seqs``: engine rows ``srows``, sequences ``seqs``."""
+
+    __slots__ = ("rows", "ctx_d", "B", "batch", "chunks", "p_ctx", "done", "done_seqs", "srows", "seqs",
+                 "T", "launch", "params", "greedy")
+
+
+class _Pending:
+    """The in-flight step of one-step-ahead scheduling: its logits ``rows`` with their ``epochs``
+    and ``seqs`` at launch, the sampled tokens on the device (``toks_d``: the next step's decode
+    ids) and on their way to the pinned ``toks_h`` behind ``ev``, log-probabilities likewise
+    (``lp``: pinned values, pinned ids, the rows' wanted counts; or None) and ``retire``, the ids
+    of the sequences whose pending token is their last."""
+
+    __slots__ = ("rows", "epochs", "seqs", "toks_d", "toks_h", "ev", "lp", "retire")
+
+    def __init__(self, rows, epochs, seqs, toks_d, toks_h, ev, lp):
+        self.rows, self.epochs, self.seqs, self.toks_d, self.toks_h = rows, epochs, seqs, toks_d, toks_h
+        self.ev, self.lp, self.retire = ev, lp, set()
+
+
 class StepBatch:
     """One step's outputs as arrays (no per-token Python objects on the hot path);
     iterating yields ``StepOutput`` lazily."""
@@ -442,6 +467,7 @@ class Engine:
         self._toks_flip = 0
         self._src_h = torch.zeros(R, dtype=torch.int64, pin_memory=cuda)
         self._src_d = torch.zeros(R, dtype=torch.int64, device=self.device)
+        self._ids_later = np.zeros(R, np.int64)  # per row: placeholder ids of a step whose ids _launch gathers
         if self.lora is not None:
             # per-token adapter slot of a step, beside the packed metadata (whose layout and upload
             # stay as they are): pinned host side, rewritten only after _wait_meta like the metadata
@@ -622,12 +648,6 @@ class Engine:
             seq.row = -1
         seq.num_cached = 0
 
-    def _params_of_running(self):
-        """Sampling params of the decode batch; a falsy ``any_random`` lets the sampler
-        take the all-greedy fast path without a per-sequence Python scan."""
-        lst = _ParamsList(s.params for s in self.running) if self.r_sampler[self._sync_rows()].any() else _ALL_GREEDY
-        return lst
-
     def _admit_ext(self, seq: Sequence) -> bool:
         """A request takes its row: its sampler-extension state.  A penalised request also takes a
         slot of the count table (False: none free, it waits) and the slot is rebuilt from the
@@ -660,11 +680,14 @@ class Engine:
         return SamplerExt(self.pen_table, slots, self.r_rep[rows], self.r_freq[rows], self.r_pres[rows], want,
                           self.model.cfg.vocab_size)
 
-    def _register_running(self, s: Sequence):
+    def _register_running(self, s: Sequence, in_flight: int = 0):
+        """Row registers of a sequence that joins the running rows; ``in_flight`` = 1: its first
+        token is still being computed (it counts in the lengths now, ``r_last`` comes with it)."""
         r, p = s.row, s.params
         self.r_random[r] = not p.greedy
-        self.r_len[r], self.r_gen[r], self.r_maxgen[r] = s.length, len(s.output), p.max_tokens
-        self.r_last[r] = s.output[-1] if s.output else s.prompt[-1]
+        self.r_len[r], self.r_gen[r], self.r_maxgen[r] = s.length + in_flight, len(s.output) + in_flight, p.max_tokens
+        if not in_flight:
+            self.r_last[r] = s.output[-1] if s.output else s.prompt[-1]
         self.r_ignore[r], self.r_hasstop[r], self.r_sid[r] = p.ignore_eos, bool(p.stop_token_ids), s.seq_id
         self._rows_add.append(r)  # s was just appended to self.running
 
@@ -747,9 +770,7 @@ class Engine:
             self.meta.fill_decode(empty, empty, np.zeros(0, dtype=np.int64), pad_to=bucket)
             self.meta.upload(bucket, bucket, self.rows_hi)
             self.graphs[bucket][0].replay()
-        if self._async and self.device.type == "cuda":
-            self._meta_ev = torch.cuda.Event()
-            self._meta_ev.record()
+        self._record_meta_ev()
         self.stats["ep_idle_steps"] += 1
 
     def _step_local(self):
@@ -761,16 +782,14 @@ class Engine:
         if self._async and (self._pending is not None or self.running):
             return self._async_step()
         if self._want_prefill():
-            if self.running and self.cfg.mixed_prefill:
-                kind, out = "mixed", self._mixed_step()
-            else:
-                kind, out = "prefill", self._prefill_step()
+            mixed = bool(self.running) and self.cfg.mixed_prefill
+            out = self._sync_step(decode=mixed, prompt=True)
             if out is not None:
                 self._decode_since_prefill = 0
-                return kind, out
+                return ("mixed" if mixed else "prefill"), out
         if self.running:
             self._decode_since_prefill += 1
-            return "decode", self._decode_step()
+            return "decode", self._sync_step(decode=True, prompt=False) or StepBatch.from_list([])
         return "idle", []
 
     # ---------------------------------------------------------- prefill --
@@ -855,107 +874,152 @@ class Engine:
         """Row i of a step's log-probability read-back -> (logprob, [(id, logprob)] * n)."""
         return float(lp_h[i, 0]), list(zip(id_h[i, 1:1 + n].tolist(), lp_h[i, 1:1 + n].tolist()))
 
-    def _take_lp(self):
-        """The last draw's log-probabilities on the host (numpy pair), or None."""
-        lp, self._last_lp = self._last_lp, None
-        return None if lp is None else (lp[0].cpu().numpy(), lp[1].cpu().numpy())
+    # ------------------------------------------------------------ steps --
+    def _build_step(self, decode: bool, prompt: bool, ids: np.ndarray):
+        """Plan one step and fill its metadata: every running row's next token (``decode``), prompt
+        chunks up to the token budget (``prompt``), or both in ONE eager ragged forward (a mixed
+        step, chunked-prefill piggybacking: the decode rows share the prefill's weight reads and
+        its larger-M GEMMs instead of paying a separate M=B pass).  A decode-only step replays
+        the graph of the smallest bucket >= B where one was captured.  ``ids``: per engine row, the
+        decode rows' input ids (``r_last``; placeholders when ``_launch`` gathers them on the
+        device).  None: nothing to run (no row decodes, fewer than ``mixed_min_chunk`` token slots
+        beside the decode rows, or no prompt chunk fits); what was preempted or admitted on the
+        way stays so."""
+        cfg, meta, n_kv = self.cfg, self.meta, self.model.n_kv
+        st = _Step()
+        budget = cfg.max_num_batched_tokens
+        rows = ctx_d = np.zeros(0, np.int32)
+        if decode:
+            rows, ctx_d = self._decode_rows()  # (may preempt)
+            if len(rows) == 0:
+                return None
+            ctx_d = ctx_d.astype(np.int32)
+            budget -= len(rows)
+        B = len(rows)
+        batch, chunks = [], []
+        if prompt:
+            if decode and budget < cfg.mixed_min_chunk:
+                return None
+            batch, chunks = self._collect_prefill(budget)
+            if not batch:
+                return None
+        p_ctx = [s.num_cached + n for s, n in zip(batch, chunks)]
+        done = [c == s.length for s, c in zip(batch, p_ctx)]
+        done_seqs = [s for s, d in zip(batch, done) if d]
+        last = ids[rows]
+        mctx = max(int(ctx_d.max()) if B else 0, max(p_ctx, default=0))
+        if batch:
+            T, nt, nl = meta.fill_mixed(rows, ctx_d, last, [s.row for s in batch], chunks, p_ctx,
+                                        [s.tokens(s.num_cached, c) for s, c in zip(batch, p_ctx)], want_logits=done)
+            st.launch = (KIND_EAGER, T, nt, nl, *plan_partitions(nt, n_kv, meta.span(mctx)), 0)
+        else:
+            bucket = next((b for b in self.buckets if b >= B), None)
+            if bucket is not None and self.graphs.get(bucket) is not None:
+                meta.fill_decode(rows, ctx_d, last, pad_to=bucket)
+                self._repad = (rows, ctx_d, last, mctx)  # EP: the group may re-pad it
+                st.launch = (KIND_GRAPH, bucket, bucket, bucket, 0, 0, bucket)
+            else:
+                meta.fill_decode(rows, ctx_d, last, pad_to=B)
+                st.launch = (KIND_EAGER, B, B, B, *plan_partitions(B, n_kv, meta.span(mctx)), 0)
+        st.T = st.launch[1]
+        self._fill_tok_slot(st.T, rows, batch, chunks)
+        # a falsy r_sampler lets the sampler take the all-greedy fast path without a per-sequence scan
+        if not self.r_sampler[rows].any() and not any(self.r_sampler[s.row] for s in done_seqs):
+            st.params = _ALL_GREEDY
+        else:
+            st.params = _ParamsList([s.params for s in (self.running if decode else ())] + [s.params for s in done_seqs])
+        st.greedy = st.params is _ALL_GREEDY
+        st.rows, st.ctx_d, st.B, st.srows = rows, ctx_d, B, self._sample_rows(rows, done_seqs)
+        st.batch, st.chunks, st.p_ctx, st.done, st.done_seqs = batch, chunks, p_ctx, done, done_seqs
+        return st
 
-    def _prefill_finish(self, batch, ctx, done, tokens, lp=None, lp_off: int = 0) -> list:
+    def _issue(self, st: _Step):
+        """Launch a built step and draw its tokens: (token ids, (log-probabilities, ids) or None),
+        both on the device; (None, None) when it has no logits row (prompt chunks, none the last
+        of its prompt)."""
+        logits = self._launch(*st.launch, greedy=st.greedy)
+        B = st.B
+        if st.batch:
+            self.stats["mixed_steps" if B else "prefill_steps"] += 1
+            self.stats["prefill_tokens"] += st.T - B
+        else:
+            self.stats["graph_steps" if st.launch[0] == KIND_GRAPH else "eager_decode_steps"] += 1
+            self.stats["decode_steps"] += 1
+        if B:
+            self.stats["decode_tokens"] += B
+        if logits is None:
+            return None, None
+        if st.launch[0] == KIND_GRAPH:
+            logits = logits[:B]  # (its padding rows)
+        toks_d = self._sample(logits, st.params, lambda: self._gen_index(st.rows, st.done_seqs), st.srows)
+        lp_d, self._last_lp = self._last_lp, None
+        return toks_d, lp_d
+
+    def _sync_step(self, decode: bool, prompt: bool):
+        """Build a step, run it and apply its tokens at once: the synchronous engine (and, under
+        one-step-ahead scheduling, prompt work while nothing decodes).  None: nothing to run."""
+        t0 = time.perf_counter()
+        st = self._build_step(decode, prompt, self.r_last)
+        if st is None:
+            return None
+        t1 = time.perf_counter()
+        toks_d, lp_d = self._issue(st)
+        toks = lp = None
+        if toks_d is not None:
+            toks = toks_d.cpu().numpy().astype(np.int64)
+            lp = None if lp_d is None else (lp_d[0].cpu().numpy(), lp_d[1].cpu().numpy())
+        elif self.device.type == "cuda":
+            torch.cuda.synchronize()
+        t2 = time.perf_counter()
+        B = st.B
+        out = self._decode_finish(st.rows, toks[:B], lp) if B else None
+        if st.batch:
+            p_out = self._chunks_done(st, [] if toks is None else toks[B:].tolist(), lp)
+            if out is None or p_out:
+                p_out = StepBatch.from_list(p_out)
+                out = p_out if out is None else StepBatch.concat(out, p_out)
+        # host-side cost accounting (us): prep before launch, device (launch..tokens), bookkeeping
+        t3 = time.perf_counter()
+        if B and st.batch:
+            self.stats["mixed_host_us"] += int(1e6 * (t1 - t0 + t3 - t2))
+            self.stats["mixed_device_us"] += int(1e6 * (t2 - t1))
+        elif B:
+            self.stats["decode_host_prep_us"] += int(1e6 * (t1 - t0))
+            self.stats["decode_device_us"] += int(1e6 * (t2 - t1))
+            self.stats["decode_host_post_us"] += int(1e6 * (t3 - t2))
+        return out
+
+    def _chunks_done(self, st: _Step, tokens=None, lp=None) -> list:
+        """The prompt chunks of a launched step: cached lengths, prefix pages, and the sequences
+        whose prompt completed join the running rows.  ``tokens`` None: their first token is still
+        in flight (one-step-ahead: the row registers count it, ``r_tokidx`` says where it will
+        be); else those tokens (and ``lp``, the step's log-probabilities), applied at once: the
+        StepOutputs are returned, and a sequence that ends with its first token never registers."""
         outs = []
-        ti = 0
-        for s, c, d in zip(batch, ctx, done):
+        for s, c, d, ti in zip(st.batch, st.p_ctx, st.done, itertools.accumulate(st.done, initial=st.B)):
             s.num_cached = c
             if self.cfg.enable_prefix_caching:
                 self._register_prefix(s, c)
-            if d:
-                self.prefilling.remove(s)
-                s.status = Status.RUNNING
-                self.running.append(s)
-                if lp is not None and s.params.logprobs is not None:
-                    entry = self._lp_entry(lp[0], lp[1], lp_off + ti, s.params.logprobs)
-                    s.logprobs.append(entry)
-                o = self._append(s, tokens[ti])
-                if lp is not None and s.params.logprobs is not None:
-                    o.logprob, o.top_logprobs = entry
-                if not o.finished:
-                    self._register_running(s)
-                outs.append(o)
-                ti += 1
+            if not d:
+                continue
+            self.prefilling.remove(s)
+            s.status = Status.RUNNING
+            self.running.append(s)
+            if tokens is None:  # (ti: the sequence's logits row in the step)
+                self._register_running(s, in_flight=1)
+                self.r_tokidx[s.row] = ti
+                continue
+            entry = None
+            if lp is not None and s.params.logprobs is not None:
+                entry = self._lp_entry(lp[0], lp[1], ti, s.params.logprobs)
+                s.logprobs.append(entry)
+            o = self._append(s, tokens[ti - st.B])
+            if entry is not None:
+                o.logprob, o.top_logprobs = entry
+            if not o.finished:
+                self._register_running(s)
+            outs.append(o)
         return outs
-
-    def _prefill_step(self):
-        batch, chunks = self._collect_prefill(self.cfg.max_num_batched_tokens)
-        if not batch:
-            return None
-        rows = [s.row for s in batch]
-        ctx = [s.num_cached + n for s, n in zip(batch, chunks)]
-        toks = [s.tokens(s.num_cached, c) for s, c in zip(batch, ctx)]
-        done = [c == s.length for s, c in zip(batch, ctx)]
-        T, nt, nl = self.meta.fill(rows, chunks, ctx, toks, want_logits=done)
-        self._fill_tok_slot(T, (), batch, chunks)
-        part, nparts = plan_partitions(nt, self.model.n_kv, self.meta.span(max(ctx)))
-        done_params = [s.params for s, d in zip(batch, done) if d]
-        logits = self._launch(KIND_EAGER, T, nt, nl, part, nparts, 0,
-                              greedy=all(p.greedy and not p.extended for p in done_params))
-        tokens = lp = None
-        if nl:
-            tokens = self._sample(logits, done_params,
-                                  lambda: [len(s.output) for s, d in zip(batch, done) if d],
-                                  [s.row for s, d in zip(batch, done) if d]).tolist()
-            lp = self._take_lp()
-        else:
-            torch.cuda.synchronize() if self.device.type == "cuda" else None
-        self.stats["prefill_steps"] += 1
-        self.stats["prefill_tokens"] += T
-        return StepBatch.from_list(self._prefill_finish(batch, ctx, done, tokens, lp))
-
-    # ------------------------------------------------------------ mixed --
-    def _mixed_step(self):
-        """Decode every running sequence AND prefill prompt chunks in ONE eager
-        forward (chunked-prefill piggybacking): the decode rows share the
-        prefill's weight reads and its larger-M GEMMs instead of paying a
-        separate M=B pass; the ragged paged-attention kernel takes both kinds
-        of tile.  Returns None (caller decodes alone) when nothing fits."""
-        t0 = time.perf_counter()
-        rows, ctx_d = self._decode_rows()
-        B = len(rows)
-        budget = self.cfg.max_num_batched_tokens - B
-        if B == 0 or budget < self.cfg.mixed_min_chunk:
-            return None
-        batch, chunks = self._collect_prefill(budget)
-        if not batch:
-            return None
-        p_rows = [s.row for s in batch]
-        p_ctx = [s.num_cached + n for s, n in zip(batch, chunks)]
-        p_toks = [s.tokens(s.num_cached, c) for s, c in zip(batch, p_ctx)]
-        done = [c == s.length for s, c in zip(batch, p_ctx)]
-        T, nt, nl = self.meta.fill_mixed(rows, ctx_d.astype(np.int32), self.r_last[rows],
-                                         p_rows, chunks, p_ctx, p_toks, want_logits=done)
-        self._fill_tok_slot(T, rows, batch, chunks)
-        part, nparts = plan_partitions(nt, self.model.n_kv, self.meta.span(max(int(ctx_d.max()), max(p_ctx))))
-        t1 = time.perf_counter()
-        done_seqs = [s for s, d in zip(batch, done) if d]
-        dparams = self._params_of_running()
-        if getattr(dparams, "all_greedy", False) and not any(self.r_sampler[s.row] for s in done_seqs):
-            params = _ALL_GREEDY
-        else:
-            params = _ParamsList([s.params for s in self.running] + [s.params for s in done_seqs])
-        logits = self._launch(KIND_EAGER, T, nt, nl, part, nparts, 0,
-                              greedy=getattr(params, "all_greedy", False))
-        toks = self._sample(logits, params, lambda: self._gen_index(rows, done_seqs),
-                            self._sample_rows(rows, done_seqs)).cpu().numpy().astype(np.int64)
-        lp = self._take_lp()
-        t2 = time.perf_counter()
-        self.stats["mixed_steps"] += 1
-        self.stats["decode_tokens"] += B
-        self.stats["prefill_tokens"] += T - B
-        d_out = self._decode_finish(rows, toks[:B], lp)
-        p_out = self._prefill_finish(batch, p_ctx, done, toks[B:].tolist(), lp, B)
-        self.stats["mixed_host_us"] += int(1e6 * (t1 - t0 + time.perf_counter() - t2))
-        self.stats["mixed_device_us"] += int(1e6 * (t2 - t1))
-        if not p_out:
-            return d_out
-        return StepBatch.concat(d_out, StepBatch.from_list(p_out))
 
     # ------------------------------------------------- async scheduling --
     # Step t+1 is built from the scheduler state as it stands after step t's LAUNCH: every
@@ -972,8 +1036,14 @@ class Engine:
         p = self._pending
         if p is None:
             return False
-        rows, ep = p["rows"], p["epochs"]
-        return bool(len(rows)) and bool((self.r_epoch[rows] == ep).any())
+        return bool(len(p.rows)) and bool((self.r_epoch[p.rows] == p.epochs).any())
+
+    def _record_meta_ev(self):
+        """One-step-ahead: the event behind this step's metadata H2D (and what else read the
+        pinned host side); ``_wait_meta`` waits for it before the next step rewrites them."""
+        if self._async and self.device.type == "cuda":
+            self._meta_ev = torch.cuda.Event()
+            self._meta_ev.record()
 
     def _wait_meta(self):
         """The previous step's metadata H2D has executed: the host buffers may be rewritten."""
@@ -988,7 +1058,7 @@ class Engine:
             # then this step's prompt work runs as a synchronous prefill step
             out = self._async_post(prev) if prev is not None else StepBatch.from_list([])
             if self._want_prefill():
-                p = self._prefill_step()
+                p = self._sync_step(decode=False, prompt=True)
                 if p is not None and len(p):
                     self._decode_since_prefill = 0
                     return "prefill", StepBatch.concat(out, p)
@@ -1014,65 +1084,17 @@ class Engine:
     def _async_launch(self, prev, mixed: bool):
         """Build, launch and advance one step; returns its pending record (None: nothing to run)."""
         t0 = time.perf_counter()
-        rows, ctx_d = self._decode_rows()
-        B = len(rows)
-        if B == 0:
-            return None
-        ctx_d = ctx_d.astype(np.int32)
-        batch, chunks = [], []
-        if mixed:
-            budget = self.cfg.max_num_batched_tokens - B
-            if budget < self.cfg.mixed_min_chunk:
-                return None
-            batch, chunks = self._collect_prefill(budget)
-            if not batch:
-                return None
         # decode input ids: on the device from the in-flight step, else the host's last token
-        gather = prev is not None and prev.get("toks_d") is not None
-        last = np.zeros(B, np.int64) if gather else self.r_last[rows]
-        dparams = self._params_of_running()
-        greedy = getattr(dparams, "all_greedy", False)
-        if mixed:
-            p_rows = [s.row for s in batch]
-            p_ctx = [s.num_cached + n for s, n in zip(batch, chunks)]
-            p_toks = [s.tokens(s.num_cached, c) for s, c in zip(batch, p_ctx)]
-            done = [c == s.length for s, c in zip(batch, p_ctx)]
-            T, nt, nl = self.meta.fill_mixed(rows, ctx_d, last, p_rows, chunks, p_ctx, p_toks, want_logits=done)
-            self._fill_tok_slot(T, rows, batch, chunks)
-            part, nparts = plan_partitions(nt, self.model.n_kv, self.meta.span(max(int(ctx_d.max()), max(p_ctx))))
-            done_seqs = [s for s, d in zip(batch, done) if d]
-            if greedy and not any(self.r_sampler[s.row] for s in done_seqs):
-                params = _ALL_GREEDY
-            else:
-                params = _ParamsList([s.params for s in self.running] + [s.params for s in done_seqs])
-            launch = (KIND_EAGER, T, nt, nl, part, nparts, 0)
-            greedy = getattr(params, "all_greedy", False)
-        else:
-            done_seqs = []
-            params = dparams
-            bucket = next((b for b in self.buckets if b >= B), None)
-            has_graph = bucket is not None and self.graphs.get(bucket) is not None
-            self._fill_tok_slot(bucket if has_graph else B, rows)
-            if has_graph:
-                self.meta.fill_decode(rows, ctx_d, last, pad_to=bucket)
-                self._repad = (rows, ctx_d, last, int(ctx_d.max()))  # EP: the group may re-pad it
-                launch = (KIND_GRAPH, bucket, bucket, bucket, 0, 0, bucket)
-            else:
-                self.meta.fill_decode(rows, ctx_d, last, pad_to=B)
-                part, nparts = plan_partitions(B, self.model.n_kv, self.meta.span(int(ctx_d.max())))
-                launch = (KIND_EAGER, B, B, B, part, nparts, 0)
-        if gather:
+        st = self._build_step(True, mixed, self.r_last if prev is None else self._ids_later)
+        if st is None:
+            return None
+        rows, B = st.rows, st.B
+        if prev is not None:
             self._src_h[:B].copy_(torch.from_numpy(self.r_tokidx[rows]))
-            self._ids_gather = (B, prev["toks_d"])
-        t1 = time.perf_counter()
-        logits = self._launch(*launch, greedy=greedy)
-        if launch[0] == KIND_GRAPH:
-            logits = logits[:B]
-        snap_rows = self._sample_rows(rows, done_seqs)
-        toks_d = self._sample(logits, params, lambda: self._gen_index(rows, done_seqs), snap_rows)
+            self._ids_gather = (B, prev.toks_d)
+        toks_d, lp_d = self._issue(st)
         n = int(toks_d.shape[0])
         toks_h = self._toks_h[self._toks_flip][:n]
-        lp_d, self._last_lp = self._last_lp, None
         lp_h = None
         if lp_d is not None:  # log-probabilities ride back beside the tokens, behind the same event
             if self._lp_h is None:
@@ -1082,61 +1104,39 @@ class Engine:
             w = lp_d[0].shape[1]
             lp_h = tuple(h[:n * w].view(n, w) for h in self._lp_h[self._toks_flip])
         self._toks_flip ^= 1
+        cuda = self.device.type == "cuda"
+        toks_h.copy_(toks_d, non_blocking=cuda)
+        if lp_h is not None:
+            lp_h[0].copy_(lp_d[0], non_blocking=cuda)
+            lp_h[1].copy_(lp_d[1], non_blocking=cuda)
         ev = None
-        if self.device.type == "cuda":
-            toks_h.copy_(toks_d, non_blocking=True)
-            if lp_h is not None:
-                lp_h[0].copy_(lp_d[0], non_blocking=True)
-                lp_h[1].copy_(lp_d[1], non_blocking=True)
+        if cuda:
             ev = torch.cuda.Event()
             ev.record()
-        else:
-            toks_h.copy_(toks_d)
-            if lp_h is not None:
-                lp_h[0].copy_(lp_d[0])
-                lp_h[1].copy_(lp_d[1])
         # advance what does not depend on token values: decode rows gained a token (pending)
         seqs_d = list(self.running)  # aligned with rows (_decode_rows synced them)
         self.r_len[rows] += 1
         self.r_gen[rows] += 1
         self.r_tokidx[rows] = np.arange(B)
-        self.stats["decode_tokens"] += B
-        if mixed:
-            self.stats["mixed_steps"] += 1
-            self.stats["prefill_tokens"] += T - B
-            self._prefill_advance(batch, p_ctx, done, B)
-        elif launch[0] == KIND_GRAPH:
-            self.stats["graph_steps"] += 1
-            self.stats["decode_steps"] += 1
-        else:
-            self.stats["eager_decode_steps"] += 1
-            self.stats["decode_steps"] += 1
-        pend = {"rows": snap_rows, "epochs": self.r_epoch[snap_rows].copy(), "seqs": seqs_d + done_seqs,
-                "toks_d": toks_d, "toks_h": toks_h, "ev": ev, "retire": set(),
-                "lp": None if lp_h is None else (lp_h[0], lp_h[1], self.r_want[snap_rows].copy())}
+        self._chunks_done(st)
+        pend = _Pending(st.srows, self.r_epoch[st.srows].copy(), seqs_d + st.done_seqs, toks_d, toks_h, ev,
+                        None if lp_h is None else (lp_h[0], lp_h[1], self.r_want[st.srows].copy()))
         self._retire_by_length(pend)
-        self.stats["async_host_us"] += int(1e6 * (t1 - t0 + time.perf_counter() - t1))
+        self.stats["async_host_us"] += int(1e6 * (time.perf_counter() - t0))
         return pend
 
-    def _prefill_advance(self, batch, ctx, done, B):
-        """Prompt chunks of a launched step: cached lengths, prefix pages, and the sequences
-        whose prompt completed join the running rows (their first token is pending)."""
-        j = 0
-        for s, c, d in zip(batch, ctx, done):
-            s.num_cached = c
-            if self.cfg.enable_prefix_caching:
-                self._register_prefix(s, c)
-            if d:
-                self.prefilling.remove(s)
-                s.status = Status.RUNNING
-                self.running.append(s)
-                r, p = s.row, s.params
-                self.r_random[r] = not p.greedy
-                self.r_len[r], self.r_gen[r], self.r_maxgen[r] = s.length + 1, len(s.output) + 1, p.max_tokens
-                self.r_ignore[r], self.r_hasstop[r], self.r_sid[r] = p.ignore_eos, bool(p.stop_token_ids), s.seq_id
-                self.r_tokidx[r] = B + j
-                self._rows_add.append(r)
-                j += 1
+    def _keep_running(self, rows, keep) -> None:
+        """Only the indices ``keep`` of the running set stay in it: ``running``, ``_outs`` and
+        ``_rows`` (``rows``: the synced ``_rows``)."""
+        run, outs = self.running, self._outs
+        if len(keep) == 0:
+            self.running, self._outs = [], []
+        elif len(keep) == 1:
+            self.running, self._outs = [run[keep[0]]], [outs[keep[0]]]
+        else:
+            get = operator.itemgetter(*keep.tolist())
+            self.running, self._outs = list(get(run)), list(get(outs))
+        self._rows = rows[keep]
 
     def _retire_by_length(self, pend):
         """Rows whose pending token is their last (max_tokens / max_model_len) leave the
@@ -1145,39 +1145,39 @@ class Engine:
         fin = (self.r_gen[rows] >= self.r_maxgen[rows]) | (self.r_len[rows] >= self.max_model_len)
         if not fin.any():
             return
-        run = self.running
-        fi = np.nonzero(fin)[0]
-        pend["retire"] = {run[i].seq_id for i in fi.tolist()}
-        keep = np.nonzero(~fin)[0]
-        get = operator.itemgetter(*keep.tolist()) if len(keep) > 1 else None
-        if len(keep) == 0:
-            self.running, self._outs = [], []
-        elif len(keep) == 1:
-            self.running, self._outs = [run[keep[0]]], [self._outs[keep[0]]]
-        else:
-            self.running, self._outs = list(get(run)), list(get(self._outs))
-        self._rows = rows[keep]
+        pend.retire = {self.running[i].seq_id for i in np.nonzero(fin)[0].tolist()}
+        self._keep_running(rows, np.nonzero(~fin)[0])
+
+    def _stop_mask(self, rows, toks, seqs) -> np.ndarray:
+        """Per row: its new token is an EOS id the request does not ignore, or one of its stop tokens."""
+        eos = self.model.cfg.eos_ids
+        is_eos = (toks == eos[0]) if len(eos) == 1 else np.isin(toks, eos)
+        fin_stop = (~self.r_ignore[rows]) & is_eos
+        for i in np.nonzero(self.r_hasstop[rows])[0].tolist():
+            if int(toks[i]) in seqs[i].params.stop_token_ids:
+                fin_stop[i] = True
+        return fin_stop
 
     def _async_post(self, pend) -> StepBatch:
         """Apply an in-flight step's tokens (waits for that step only)."""
         t0 = time.perf_counter()
-        if pend["ev"] is not None:
-            pend["ev"].synchronize()
-        rows = pend["rows"]
+        if pend.ev is not None:
+            pend.ev.synchronize()
+        rows = pend.rows
         n = len(rows)
-        toks = pend["toks_h"][:n].numpy().copy() if n else np.zeros(0, np.int64)
-        lp = pend["lp"]
+        toks = pend.toks_h[:n].numpy().copy() if n else np.zeros(0, np.int64)
+        lp = pend.lp
         if lp is not None:
             lp = (lp[0].numpy().copy(), lp[1].numpy().copy(), lp[2])
-        alive = self.r_epoch[rows] == pend["epochs"]
+        alive = self.r_epoch[rows] == pend.epochs
         if not alive.all():
             ai = np.nonzero(alive)[0]
             rows, toks = rows[ai], toks[ai]
-            seqs = [pend["seqs"][i] for i in ai.tolist()]
+            seqs = [pend.seqs[i] for i in ai.tolist()]
             if lp is not None:  # a released row's log-probabilities go with its token
                 lp = tuple(a[ai] for a in lp)
         else:
-            seqs = pend["seqs"]
+            seqs = pend.seqs
         if not len(rows):
             return StepBatch.from_list([])
         lps = self._deliver_lp(seqs, lp, lp[2]) if lp is not None else None
@@ -1187,13 +1187,8 @@ class Engine:
                 s.first_token_time = now
         collections.deque(map(list.append, [s.output for s in seqs], toks.tolist()), maxlen=0)
         self.r_last[rows] = toks
-        eos = self.model.cfg.eos_ids
-        is_eos = (toks == eos[0]) if len(eos) == 1 else np.isin(toks, eos)
-        fin_stop = (~self.r_ignore[rows]) & is_eos
-        for i in np.nonzero(self.r_hasstop[rows])[0].tolist():
-            if int(toks[i]) in seqs[i].params.stop_token_ids:
-                fin_stop[i] = True
-        retire = pend["retire"]
+        fin_stop = self._stop_mask(rows, toks, seqs)
+        retire = pend.retire
         fin_len = np.zeros(len(rows), bool)
         if retire:
             fin_len = np.fromiter((s.seq_id in retire for s in seqs), dtype=bool, count=len(seqs))
@@ -1270,44 +1265,6 @@ class Engine:
             self._outs.extend(s.output for s in self.running[-n:])
             self._rows_add.clear()
         return self._rows
-
-    def _decode_step(self):
-        t0 = time.perf_counter()
-        rows, ctx = self._decode_rows()
-        B = len(rows)
-        if B == 0:
-            return StepBatch.from_list([])
-        ctx = ctx.astype(np.int32)
-        last = self.r_last[rows]
-        bucket = next((b for b in self.buckets if b >= B), None)
-        g = self.graphs.get(bucket) if bucket is not None else None
-        params = self._params_of_running()
-        greedy = getattr(params, "all_greedy", False)
-        self._fill_tok_slot(bucket if g is not None else B, rows)
-        if g is not None:
-            self.meta.fill_decode(rows, ctx, last, pad_to=bucket)
-            self._repad = (rows, ctx, last, int(ctx.max()))
-            t1 = time.perf_counter()
-            logits = self._launch(KIND_GRAPH, bucket, bucket, bucket, 0, 0, bucket, greedy=greedy)[:B]
-            self.stats["graph_steps"] += 1
-        else:
-            self.meta.fill_decode(rows, ctx, last, pad_to=B)
-            part, nparts = plan_partitions(B, self.model.n_kv, self.meta.span(int(ctx.max())))
-            t1 = time.perf_counter()
-            logits = self._launch(KIND_EAGER, B, B, B, part, nparts, 0, greedy=greedy)
-            self.stats["eager_decode_steps"] += 1
-        toks = self._sample(logits, params, lambda: self._gen_index(rows, ()), rows).cpu().numpy().astype(np.int64)
-        lp = self._take_lp()
-        t2 = time.perf_counter()
-        self.stats["decode_steps"] += 1
-        self.stats["decode_tokens"] += B
-        outs = self._decode_finish(rows, toks, lp)
-        t3 = time.perf_counter()
-        # host-side cost accounting (us): prep before launch, device (launch..tokens), bookkeeping
-        self.stats["decode_host_prep_us"] += int(1e6 * (t1 - t0))
-        self.stats["decode_device_us"] += int(1e6 * (t2 - t1))
-        self.stats["decode_host_post_us"] += int(1e6 * (t3 - t2))
-        return outs
 
     def _fill_tok_slot(self, T: int, d_rows, batch=(), chunks=()) -> None:
         """The step's adapter slot per token, in the metadata's token order: the decode rows, then
@@ -1392,14 +1349,8 @@ class Engine:
         self.r_gen[rows] += 1
         self.r_last[rows] = toks
         fin_len = (self.r_gen[rows] >= self.r_maxgen[rows]) | (self.r_len[rows] >= self.max_model_len)
-        eos = self.model.cfg.eos_ids
-        is_eos = (toks == eos[0]) if len(eos) == 1 else np.isin(toks, eos)
-        fin_stop = (~self.r_ignore[rows]) & is_eos
         run = self.running
-        hs = np.nonzero(self.r_hasstop[rows])[0]
-        for i in hs.tolist():
-            if int(toks[i]) in run[i].params.stop_token_ids:
-                fin_stop[i] = True
+        fin_stop = self._stop_mask(rows, toks, run)
         fin = fin_stop | fin_len
         # one token onto every running sequence's output list, at C speed
         collections.deque(map(list.append, self._outs, toks.tolist()), maxlen=0)
@@ -1411,15 +1362,7 @@ class Engine:
             done = [run[i] for i in fi.tolist()]
             for i, s in zip(fi.tolist(), done):
                 reasons[s.seq_id] = "stop" if fin_stop[i] else "length"
-            keep = np.nonzero(~fin)[0]
-            if len(keep) == 0:
-                self.running, self._outs = [], []
-            elif len(keep) == 1:
-                self.running, self._outs = [run[keep[0]]], [self._outs[keep[0]]]
-            else:
-                get = operator.itemgetter(*keep.tolist())
-                self.running, self._outs = list(get(run)), list(get(self._outs))
-            self._rows = rows[keep]
+            self._keep_running(rows, np.nonzero(~fin)[0])
             for s in done:
                 self._finish(s, reasons[s.seq_id])
         return StepBatch(sids, toks, fin, reasons, lps)
@@ -1474,9 +1417,7 @@ class Engine:
             self.step_sync.send(self, kind, T, nt, nl, part, nparts, bucket, npt, int(greedy))
             self.stats["tp_sync_us"] += int(1e6 * (time.perf_counter() - t0))
             self.stats["tp_sync_calls"] += 1
-        if self._async and self.device.type == "cuda":
-            self._meta_ev = torch.cuda.Event()
-            self._meta_ev.record()
+        self._record_meta_ev()
         return self._execute(kind, T, nt, nl, part, nparts, bucket, npt, greedy)
 
     def _ep_agree(self, kind, T, nt, nl, part, nparts, bucket):
@@ -1552,6 +1493,8 @@ class Engine:
 
     def _sample_rows(self, rows, done_seqs):
         """Engine rows of a step's logits rows: the decode rows, then the completed prompts."""
+        if not done_seqs:
+            return rows  # (``_rows`` as it stood: it is replaced, never written in place)
         return np.concatenate([rows, np.asarray([s.row for s in done_seqs], dtype=rows.dtype)])
 
     def _gen_index(self, rows, done_seqs):
@@ -1604,6 +1547,13 @@ class Engine:
         empty = np.zeros(0, dtype=np.int32)
         t0 = time.perf_counter()
         verbose = False
+
+        def capture(**kw):
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, pool=self.graph_pool, stream=stream):
+                logits = m.logits_local(m.forward(ids, meta, self.kv, **kw))
+            return g, logits
+
         with torch.cuda.stream(stream):
             for bi, b in enumerate(sorted(self.buckets, reverse=True)):
                 self.meta.fill_decode(empty, empty, np.zeros(0, dtype=np.int64), pad_to=b)
@@ -1620,10 +1570,7 @@ class Engine:
                 if verbose:
                     print(f"[engine] capturing decode graph {bi + 1}/{len(self.buckets)} (batch {b}) "
                           f"at {time.perf_counter() - t0:.1f} s", file=sys.stderr, flush=True)
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, pool=self.graph_pool, stream=stream):
-                    logits = m.logits_local(m.forward(ids, meta, self.kv))
-                self.graphs[b] = (g, logits)
+                self.graphs[b] = capture()
                 if self.lora is not None:
                     # second family: the LoRA forward of the same bucket, replayed by decode steps
                     # with an adapter row.  It reads tok_slot and the slot stacks through fixed
@@ -1632,10 +1579,7 @@ class Engine:
                     step = self.lora.step(self._ts_d[:b])
                     m.logits_local(m.forward(ids, meta, self.kv, lora=step))
                     stream.synchronize()
-                    g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g, pool=self.graph_pool, stream=stream):
-                        logits = m.logits_local(m.forward(ids, meta, self.kv, lora=step))
-                    self.graphs_lora[b] = (g, logits)
+                    self.graphs_lora[b] = capture(lora=step)
         torch.cuda.current_stream(self.device).wait_stream(stream)
         torch.cuda.synchronize(self.device)
         self.stats["graph_capture_ms"] = int(1e3 * (time.perf_counter() - t0))
