@@ -160,6 +160,109 @@ __global__ void __launch_bounds__(64) argmax_keys_kernel(long* __restrict__ out,
   }
 }
 
+// the float of a key (fkey's inverse)
+__device__ __forceinline__ float key_float(uint32_t k) {
+  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+
+// exp((x - vmax) / T) with T -> 0+ taken as its limit: the maximum weighs 1 whatever 1 / T is.
+// For a T whose reciprocal is +inf (a subnormal; every T > 0 is a sampling row) 0 * inf would be
+// NaN; this way the other weights are exp(-inf) = 0 and the draw is uniform over the tied maxima.
+__device__ __forceinline__ float soft_w(float x, float vmax, float invT) {
+  const float d = x - vmax;
+  return d == 0.f ? 1.f : __expf(d * invT);
+}
+
+// The K candidates of a finished radix select over src[0, len): `prefix` is the K-th largest key and
+// `remaining` of the K places are left for the keys equal to it.  put(p, x, j) stores src[j] = x as
+// candidate p.  Equal logits go to the LOWER index, always: which ids are drawn from must not depend
+// on the order in which threads arrive (a seeded request reproduces; greedy and top_k = 1 rows
+// answer as ops.argmax does).  Two forms, both block-uniform in their arguments and synchronised
+// at their end.
+//
+// gather_ordered: candidate p is the p-th in INDEX order.  Each wave owns one contiguous share of
+// src: a counting pass, then a pass that ranks the keys above and at the threshold in index order
+// (the lower waves' counts + a ballot prefix).  s_wave: 2 words per wave, LDS.
+template <class Put>
+__device__ __forceinline__ void gather_ordered(const float* src, int len, uint32_t prefix, uint32_t remaining,
+                                               uint32_t* s_wave, Put put) {
+  constexpr int kU = 4;  // 64-wide sweeps in flight per trip of the ranking pass
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  const int q = ((len + nw - 1) / nw + 63) & ~63;
+  const int b0 = min(len, wid * q), b1 = min(len, b0 + q);
+  uint32_t gt = 0, eq = 0;
+  for (int j = b0 + lane; j < b1; j += 64) {
+    const uint32_t k = fkey(src[j]);
+    gt += k > prefix;
+    eq += k == prefix;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    gt += __shfl_xor(gt, o, 64);
+    eq += __shfl_xor(eq, o, 64);
+  }
+  if (lane == 0) { s_wave[wid] = gt; s_wave[nw + wid] = eq; }
+  __syncthreads();
+  uint32_t gt_base = 0, eq_base = 0;
+  for (int w = 0; w < wid; ++w) { gt_base += s_wave[w]; eq_base += s_wave[nw + w]; }
+  const unsigned long long below = (1ull << lane) - 1;
+  for (int jb = b0; jb < b1; jb += 64 * kU) {
+    float x[kU];
+#pragma unroll
+    for (int u = 0; u < kU; ++u) {
+      const int j = jb + 64 * u + lane;
+      x[u] = j < b1 ? src[j] : 0.f;
+    }
+#pragma unroll
+    for (int u = 0; u < kU; ++u) {
+      const int j = jb + 64 * u + lane;
+      const uint32_t k = fkey(x[u]);
+      const bool is_gt = j < b1 && k > prefix, is_eq = j < b1 && k == prefix;
+      const unsigned long long m_gt = __ballot(is_gt), m_eq = __ballot(is_eq);
+      const uint32_t r_eq = eq_base + (uint32_t)__popcll(m_eq & below);
+      if (is_gt || (is_eq && r_eq < remaining))
+        put(gt_base + (uint32_t)__popcll(m_gt & below) + min(r_eq, remaining), x[u], j);
+      gt_base += (uint32_t)__popcll(m_gt);
+      eq_base += (uint32_t)__popcll(m_eq);
+    }
+  }
+  __syncthreads();
+}
+
+// gather_listed: for a caller that sorts its candidates anyway, and at most kMaxCand keys at the
+// threshold (eq_total of them).  One 256-stride pass: the keys above the threshold take their
+// places by atomics, the indices of the keys AT it are listed (tie: kMaxCand ints, LDS); then every
+// listed index counts the listed indices below it and the ranks < remaining are stored.  Without a
+// contest (eq_total == remaining, the rule on tie-free logits) that is the one pass and a few reads.
+template <class Put>
+__device__ __forceinline__ void gather_listed(const float* src, int len, uint32_t K, uint32_t prefix,
+                                              uint32_t remaining, uint32_t eq_total, uint32_t* s_cnt, int* tie,
+                                              Put put) {
+  const uint32_t n_gt = K - remaining;
+  if (threadIdx.x == 0) { s_cnt[0] = 0; s_cnt[1] = 0; }
+  __syncthreads();
+  for (int j = threadIdx.x; j < len; j += blockDim.x) {
+    const float x = src[j];
+    const uint32_t k = fkey(x);
+    if (k > prefix) {
+      const uint32_t p = atomicAdd(&s_cnt[0], 1u);
+      if (p < n_gt) put(p, x, j);
+    } else if (k == prefix) {
+      const uint32_t p = atomicAdd(&s_cnt[1], 1u);
+      if (p < eq_total) tie[p] = j;
+    }
+  }
+  __syncthreads();
+  const float xk = key_float(prefix);
+  for (uint32_t t = threadIdx.x; t < eq_total; t += blockDim.x) {
+    const int j = tie[t];
+    uint32_t r = 0;
+    for (uint32_t o = 0; o < eq_total; ++o) r += tie[o] < j;
+    if (r < remaining) put(n_gt + r, xk, j);
+  }
+  __syncthreads();
+}
+
 // idx_map (optional): the row holds pre-selected candidates (sample_presel_kernel) and
 // idx_map[row * ld + j] is candidate j's vocabulary index (-inf padding maps to 0x7fffffff)
 __global__ void __launch_bounds__(kSampleThreads) sample_kernel(
@@ -173,7 +276,7 @@ __global__ void __launch_bounds__(kSampleThreads) sample_kernel(
   __shared__ float scan[kMaxCand];
   __shared__ float sv[kSampleThreads / 64];
   __shared__ int si[kSampleThreads / 64];
-  __shared__ uint32_t s_prefix, s_remaining, s_cnt_gt, s_cnt_eq;
+  __shared__ uint32_t s_prefix, s_remaining, s_eq, s_cnt[2], s_wave[2 * kSampleThreads / 64];
 
   const int row_id = blockIdx.x;
   const float* row = logits + row_id * ld;
@@ -209,28 +312,24 @@ __global__ void __launch_bounds__(kSampleThreads) sample_kernel(
       }
       s_prefix = prefix | ((uint32_t)d << shift);
       s_remaining = remaining - above;
+      s_eq = hist[d];  // after the last digit: the keys equal to the K-th
     }
     __syncthreads();
     prefix = s_prefix;
     remaining = s_remaining;
     mask |= 0xffu << shift;
   }
-  // keys > prefix: K - remaining of them; keys == prefix: take `remaining`
-  if (threadIdx.x == 0) { s_cnt_gt = 0; s_cnt_eq = 0; }
-  __syncthreads();
-  const uint32_t n_gt = (uint32_t)K - remaining;
-  for (int j = threadIdx.x; j < V; j += blockDim.x) {
-    const float x = row[j];
-    const uint32_t k = fkey(x);
-    if (k > prefix) {
-      const uint32_t p = atomicAdd(&s_cnt_gt, 1u);
-      if (p < n_gt) { cv[p] = x; ci[p] = idx_map ? idx_map[row_id * ld + j] : j; }
-    } else if (k == prefix) {
-      const uint32_t p = atomicAdd(&s_cnt_eq, 1u);
-      if (p < remaining) { cv[n_gt + p] = x; ci[n_gt + p] = idx_map ? idx_map[row_id * ld + j] : j; }
-    }
-  }
-  __syncthreads();
+  // keys > prefix: K - remaining of them; keys == prefix: the `remaining` lowest indices (of the
+  // pre-selection's candidates: positions, which it wrote in index order).  scan is free until
+  // the prefix sum: it holds the tie list.
+  auto put = [&](uint32_t p, float x, int j) {
+    cv[p] = x;
+    ci[p] = idx_map ? idx_map[row_id * ld + j] : j;
+  };
+  if (s_eq <= (uint32_t)kMaxCand)
+    gather_listed(row, V, (uint32_t)K, prefix, remaining, s_eq, s_cnt, reinterpret_cast<int*>(scan), put);
+  else
+    gather_ordered(row, V, prefix, remaining, s_wave, put);
   // pad to a power of two for the bitonic network
   int P = 1;
   while (P < K) P <<= 1;
@@ -258,7 +357,7 @@ __global__ void __launch_bounds__(kSampleThreads) sample_kernel(
   const float vmax = cv[0];
   const float invT = 1.f / T;
   for (int j = threadIdx.x; j < P; j += blockDim.x)
-    scan[j] = j < K ? __expf((cv[j] - vmax) * invT) : 0.f;
+    scan[j] = j < K ? soft_w(cv[j], vmax, invT) : 0.f;
   __syncthreads();
   for (int o = 1; o < P; o <<= 1) {
     float add[kMaxCand / kSampleThreads];
@@ -272,15 +371,13 @@ __global__ void __launch_bounds__(kSampleThreads) sample_kernel(
   if (threadIdx.x == 0) {
     const float total = scan[K - 1];
     const float p = top_ps[row_id];
-    int cut = K - 1;
-    if (p < 1.f) {
-      const float lim = p * total;
-      int lo = 0, hi = K - 1;  // first index with scan >= lim
-      while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (scan[mid] >= lim) hi = mid; else lo = mid + 1;
-      }
-      cut = lo;
+    // the nucleus ends at the first index whose mass reaches p of the total; at p = 1 that is the
+    // last candidate with a weight, never the -inf padding behind a vocabulary shorter than K
+    const float lim = p < 1.f ? p * total : total;
+    int cut = 0, top = K - 1;
+    while (cut < top) {
+      const int mid = (cut + top) >> 1;
+      if (scan[mid] >= lim) top = mid; else cut = mid + 1;
     }
     const float target = uniform[row_id] * scan[cut];
     int lo = 0, hi = cut;  // first index with scan > target
@@ -296,9 +393,11 @@ __global__ void __launch_bounds__(kSampleThreads) sample_kernel(
 // 128k vocabulary (5 dependent passes over 512 KB).  Stage 1 splits each row over S
 // workgroups: a workgroup stages its slice (<= kPreselSlice floats) in LDS once, radix-
 // selects the slice's own top-K (K = the row's top_k, capped at kMaxCand) and writes them as
-// kMaxCand (value, vocab index) candidates (-inf padding).  The row's global top-K is inside
-// the union of the slices' top-K, so stage 2 (sample_kernel over the S * kMaxCand candidates,
-// idx_map = their indices) draws from the same distribution with the same uniform.
+// kMaxCand (value, vocab index) candidates in index order (-inf padding behind them).  The
+// row's global top-K (ties at the K-th value to the lowest indices) is inside the union of the
+// slices' top-K under the same rule, and a candidate's position grows with its index, so stage 2
+// (sample_kernel over the S * kMaxCand candidates, idx_map = their indices) selects the same K
+// and draws the same token with the same uniform as the single-stage kernel.
 constexpr int kPreselSlice = 8192;
 
 __global__ void __launch_bounds__(kSampleThreads) sample_presel_kernel(
@@ -306,7 +405,7 @@ __global__ void __launch_bounds__(kSampleThreads) sample_presel_kernel(
     const float* __restrict__ temps, const int* __restrict__ top_ks, int per) {
   __shared__ float sl[kPreselSlice];
   __shared__ uint32_t hist[256];
-  __shared__ uint32_t s_prefix, s_remaining, s_cnt_gt, s_cnt_eq;
+  __shared__ uint32_t s_prefix, s_remaining, s_wave[2 * kSampleThreads / 64];
   const int s = blockIdx.x, row_id = blockIdx.y, S = gridDim.x;
   const int j0 = s * per, len = max(0, min(per, V - j0));
   const size_t base = ((size_t)row_id * S + s) * kMaxCand;
@@ -342,20 +441,12 @@ __global__ void __launch_bounds__(kSampleThreads) sample_presel_kernel(
     remaining = s_remaining;
     mask |= 0xffu << shift;
   }
-  if (threadIdx.x == 0) { s_cnt_gt = 0; s_cnt_eq = 0; }
-  __syncthreads();
-  const uint32_t n_gt = K > 0 ? (uint32_t)K - remaining : 0;
-  for (int j = threadIdx.x; j < len && K > 0; j += blockDim.x) {
-    const float x = sl[j];
-    const uint32_t k = fkey(x);
-    if (k > prefix) {
-      const uint32_t p = atomicAdd(&s_cnt_gt, 1u);
-      if (p < n_gt) { cand_v[base + p] = x; cand_i[base + p] = j0 + j; }
-    } else if (k == prefix) {
-      const uint32_t p = atomicAdd(&s_cnt_eq, 1u);
-      if (p < remaining) { cand_v[base + n_gt + p] = x; cand_i[base + n_gt + p] = j0 + j; }
-    }
-  }
+  // the slice's K candidates in INDEX order, ties at the K-th value to the lowest indices
+  if (K > 0)
+    gather_ordered(sl, len, prefix, remaining, s_wave, [&](uint32_t p, float x, int j) {
+      cand_v[base + p] = x;
+      cand_i[base + p] = j0 + j;
+    });
   for (int j = max(K, 0) + threadIdx.x; j < kMaxCand; j += blockDim.x) {
     cand_v[base + j] = -INFINITY;
     cand_i[base + j] = 0x7fffffff;
@@ -381,11 +472,7 @@ __global__ void __launch_bounds__(kSampleThreads) sample_presel_kernel(
 constexpr float kFixOne = 1099511627776.0f;  // 2^40: the row max's fixed-point weight
 
 __device__ __forceinline__ unsigned long long fix_w(float x, float vmax, float invT) {
-  return (unsigned long long)(__expf((x - vmax) * invT) * kFixOne);
-}
-
-__device__ __forceinline__ float key_float(uint32_t k) {
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+  return (unsigned long long)(soft_w(x, vmax, invT) * kFixOne);
 }
 
 __global__ void __launch_bounds__(kSampleThreads) sample_full_kernel(

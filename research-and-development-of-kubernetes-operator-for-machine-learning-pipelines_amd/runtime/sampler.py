@@ -111,17 +111,20 @@ def seeded_uniform(seed: int, index: int) -> float:
 def _sample_full_row(l: torch.Tensor, T: float, k: int, p: float, u: float) -> int:
     """One row without a candidate bound (top_k = 0 or > MAX_TOP_K), fp64: members = the top-k
     by value (ties at the k-th value all kept) or the whole vocabulary; nucleus = the smallest
-    prefix of the members sorted by value (ties by index) whose softmax mass reaches p of the
-    members' mass; the draw = inverse CDF over the nucleus in vocabulary order."""
+    prefix of the members sorted by value (equal logits by lower id) whose softmax mass reaches
+    p of the members' mass; the draw = inverse CDF over the nucleus in vocabulary order.  Every
+    T > 0 is a sampling row: as T -> 0+ the weights become the indicator of the row maximum and
+    the draw is uniform over the tied maxima."""
     V = l.numel()
     l = l.double()
     member = torch.ones(V, dtype=torch.bool)
+    if 0 < k < V or p < 1.0:
+        order = torch.sort(-l, stable=True).indices  # descending value, equal logits by lower id
     if 0 < k < V:
-        member = l >= torch.topk(l, k).values[-1]
+        member = l >= l[order[k - 1]]
     w = torch.exp((l - l.max()) / T) * member
     nucleus = member
     if p < 1.0:
-        order = torch.sort(-l, stable=True).indices  # descending value, ties by index
         cum = torch.cumsum(w[order], 0)
         keep = min(int((cum < p * float(cum[-1])).sum()) + 1, int(member.sum()))
         nucleus = torch.zeros(V, dtype=torch.bool)
@@ -132,39 +135,40 @@ def _sample_full_row(l: torch.Tensor, T: float, k: int, p: float, u: float) -> i
 
 def sample_reference(logits: torch.Tensor, temps: torch.Tensor, top_k: torch.Tensor,
                      top_p: torch.Tensor, uniform: torch.Tensor) -> torch.Tensor:
-    """Plain-torch sampler with the kernels' semantics (sampling.hip).
+    """Plain-torch sampler, fp64: the contract the kernels of sampling.hip are held to.
 
-    temps/top_k/top_p/uniform: [n]; rows with temp <= 0 are greedy (argmax, ties to the lowest
-    index).  0 < top_k <= MAX_TOP_K: candidates = the top-k logits; probabilities =
-    softmax(l / T) over them; top-p keeps the smallest prefix with mass >= p; the token is the
-    first candidate whose cumulative (renormalised) mass exceeds u.  top_k = 0 (or larger than
-    MAX_TOP_K): the softmax over the WHOLE vocabulary (``_sample_full_row``)."""
+    temps/top_k/top_p/uniform: [n].  Equal logits are ordered by LOWER ID, everywhere: the
+    order below is a stable descending sort of the row.  Rows with temp <= 0 are greedy (the
+    first of that order).  Every temp > 0 is a sampling row, however small: as T -> 0+ the
+    weights exp((l - max) / T) become the indicator of the maximum and the draw is uniform over
+    the tied maxima among the candidates.  0 < top_k <= MAX_TOP_K: candidates = the first
+    min(top_k, V) of the order (exactly that many: ties at the k-th value go to the lower
+    ids); top-p keeps the smallest prefix of them whose mass reaches p of the candidates' mass;
+    the token is the first candidate of that prefix, in the same order, whose cumulative mass
+    exceeds u times the prefix's.  top_k = 0 (or larger than MAX_TOP_K): the softmax over the
+    WHOLE vocabulary, ties at the k-th value all kept (``_sample_full_row``)."""
     n, V = logits.shape
     out = torch.empty(n, dtype=torch.int64, device=logits.device)
     kmax = min(MAX_TOP_K, V)
-    lf = logits.float()
-    vals, idx = torch.topk(lf, kmax, dim=-1)  # sorted desc
+    lf = logits.float().cpu()
     for i in range(n):
-        if float(temps[i]) <= 0.0:
-            out[i] = lf[i].argmax()
+        T, k = float(temps[i]), int(top_k[i])
+        if T > 0.0 and (k <= 0 or k > MAX_TOP_K):
+            out[i] = _sample_full_row(lf[i], T, k, float(top_p[i]), float(uniform[i]))
             continue
-        k = int(top_k[i])
-        if k <= 0 or k > MAX_TOP_K:
-            out[i] = _sample_full_row(lf[i].cpu(), float(temps[i]), k, float(top_p[i]), float(uniform[i]))
+        if T <= 0.0:
+            out[i] = lf[i].argmax()  # the first of the maxima
             continue
+        order = torch.sort(-lf[i], stable=True).indices  # descending value, equal logits by lower id
         k = min(k, kmax)
-        v = vals[i, :k] / float(temps[i])
-        p = torch.softmax(v, dim=-1)
-        c = torch.cumsum(p, dim=-1)
+        v = lf[i][order[:k]].double()
+        c = torch.cumsum(torch.exp((v - v[0]) / T), dim=-1)
         pp = float(top_p[i])
+        keep = k
         if pp < 1.0:
-            keep = int((c < pp).sum().item()) + 1
-            keep = min(keep, k)
-            p = p[:keep] / c[keep - 1]
-            c = torch.cumsum(p, dim=-1)
-        j = int((c <= float(uniform[i])).sum().item())
-        j = min(j, c.numel() - 1)
-        out[i] = idx[i, j]
+            keep = min(int((c < pp * float(c[-1])).sum()) + 1, k)
+        j = int((c[:keep] <= float(uniform[i]) * float(c[keep - 1])).sum())
+        out[i] = order[min(j, keep - 1)]
     return out
 
 
