@@ -87,6 +87,7 @@ class CanaryPolicy:
 
 
 KV_CACHE_DTYPES = ("bf16", "fp8")  # spec.kvCacheDtype (manifests/crd.yaml's enum)
+MAX_SPECULATIVE_TOKENS = 7         # spec.speculativeTokens (manifests/crd.yaml's maximum; runtime/spec.py)
 
 
 @dataclass(frozen=True)
@@ -108,6 +109,8 @@ class ModelSpec:
     adapters: tuple = ()
     # KV cache element type of the LLM runtime: None / "bf16", or "fp8" (e4m3fn pages + row scales)
     kv_cache_dtype: str | None = None
+    # draft tokens per step of the LLM runtime's prompt-lookup speculative decoding: None / 0 = off, 1..7
+    speculative_tokens: int | None = None
 
     @classmethod
     def from_spec(cls, spec: dict) -> "ModelSpec":
@@ -124,7 +127,8 @@ class ModelSpec:
                    canary=CanaryPolicy.from_spec(spec),
                    adapters=tuple((a.get("name"), a.get("uri")) for a in (spec.get("adapters") or [])
                                   if isinstance(a, dict)),
-                   kv_cache_dtype=spec.get("kvCacheDtype"))
+                   kv_cache_dtype=spec.get("kvCacheDtype"),
+                   speculative_tokens=spec.get("speculativeTokens"))
 
     def validate(self) -> list[str]:
         errs = []
@@ -148,6 +152,17 @@ class ModelSpec:
                 errs.append(f"spec.kvCacheDtype must be one of {list(KV_CACHE_DTYPES)}, not {self.kv_cache_dtype!r}")
             elif self.kv_cache_dtype == "fp8" and int(self.expert_parallel or 1) > 1:
                 errs.append("spec.kvCacheDtype fp8 needs expertParallel = 1 (no fp8 KV cache for MoE / EP engines)")
+        k = self.speculative_tokens
+        if k is not None:
+            if isinstance(k, bool) or not isinstance(k, int) or not 0 <= k <= MAX_SPECULATIVE_TOKENS:
+                errs.append(f"spec.speculativeTokens must be an integer in [0, {MAX_SPECULATIVE_TOKENS}], not {k!r}")
+            elif k > 0:
+                if int(self.tensor_parallel or 1) > 1 or int(self.expert_parallel or 1) > 1:
+                    errs.append("spec.speculativeTokens needs tensorParallel = 1 and expertParallel = 1")
+                if self.kv_cache_dtype == "fp8":
+                    errs.append("spec.speculativeTokens is not supported with kvCacheDtype fp8")
+                if self.adapters:
+                    errs.append("spec.speculativeTokens is not supported with adapters")
         return errs
 
 

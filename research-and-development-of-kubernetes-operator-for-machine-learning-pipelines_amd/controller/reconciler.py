@@ -286,6 +286,8 @@ class MlflowModelReconciler:
                 engine_args["max_num_seqs"] = spec.max_num_seqs
             if spec.kv_cache_dtype and runtime == seldon.RUNTIME_LLM:
                 engine_args["kv_cache_dtype"] = spec.kv_cache_dtype  # -> MLOP_ENGINE_KV_CACHE_DTYPE
+            if spec.speculative_tokens and runtime == seldon.RUNTIME_LLM:
+                engine_args["spec_tokens"] = spec.speculative_tokens  # -> MLOP_ENGINE_SPEC_TOKENS
             preds.append(seldon.build_predictor(
                 v, uri, spec.minio_secret, traffic, runtime=runtime, replicas=spec.replicas, placement=placement,
                 image=self.settings.runtime_image, gpu_resource=self.settings.gpu_resource,

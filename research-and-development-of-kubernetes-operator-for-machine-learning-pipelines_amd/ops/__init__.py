@@ -831,8 +831,35 @@ def token_logprobs(out_lp: torch.Tensor, out_id: torch.Tensor, logits: torch.Ten
     torch.ops.mlop.token_logprobs(out_lp, out_id, logits, chosen.contiguous(), want)
 
 
+def spec_accept(sampled: torch.Tensor, q_start, drafts, nd, rows, hist, hist_len, out) -> None:
+    """The accept rule of a (verify) step, per row i (runtime/spec.py ``accept_reference``): the
+    row's tokens are sampled[q_start[i] .. + nd[i]]; a = the leading drafts[i, :nd[i]] they
+    reproduce; sampled[q_start[i] .. + a] are appended to hist[rows[i]] (hist_len advanced) and
+    written to out[i, 2:], out[i, 0] = a + 1.  ``out``: int32 [B, 2 + (k + 1) + k]."""
+    if not hist.is_cuda:
+        from ..runtime.spec import spec_accept_cpu
+
+        return spec_accept_cpu(sampled.numpy(), q_start.numpy(), drafts.numpy(), nd.numpy(), rows.numpy(),
+                               hist.numpy(), hist_len.numpy(), out.numpy())
+    _need_gpu()
+    torch.ops.mlop.spec_accept(sampled.contiguous(), q_start, drafts, nd, rows, hist, hist_len, out)
+
+
+def spec_propose(hist, hist_len, rows, cap, n_max: int, n_min: int, out) -> None:
+    """Prompt-lookup drafts per row i (runtime/spec.py ``propose_reference`` on
+    hist[rows[i], :hist_len[rows[i]]] with cap[i] <= k): out[i, 1] = their count,
+    out[i, 2 + (k + 1):] = the drafts."""
+    if not hist.is_cuda:
+        from ..runtime.spec import spec_propose_cpu
+
+        return spec_propose_cpu(hist.numpy(), hist_len.numpy(), rows.numpy(), cap.numpy(), int(n_max), int(n_min),
+                                out.numpy())
+    _need_gpu()
+    torch.ops.mlop.spec_propose(hist, hist_len, rows, cap, int(n_max), int(n_min), out)
+
+
 __all__ = ["argmax", "sample", "penalty_table", "penalty_reset", "penalty_update", "apply_penalties",
-           "token_logprobs", "load","available", "library_path", "rmsnorm", "add_rmsnorm", "rope_cache",
+           "token_logprobs", "spec_accept", "spec_propose", "load","available", "library_path", "rmsnorm", "add_rmsnorm", "rope_cache",
            "silu_mul", "embedding", "paged_attention", "ref"]
 
 

@@ -828,6 +828,50 @@ void penalty_update(Tensor table, int64_t vocab, Tensor slots, Tensor tokens) {
                               cur_stream());
 }
 
+// ---- speculative decoding by prompt lookup (spec.hip) ----
+int64_t check_spec_state(const Tensor& hist, const Tensor& hist_len, const Tensor& rows, const Tensor& out) {
+  check_i32(hist, "hist");
+  check_i32(hist_len, "hist_len");
+  check_i32(rows, "rows");
+  check_i32(out, "out");
+  TORCH_CHECK(hist.dim() == 2 && hist_len.dim() == 1 && hist_len.size(0) == hist.size(0),
+              "hist must be int32 [R, max_len] and hist_len int32 [R]");
+  const int64_t B = rows.numel();
+  TORCH_CHECK(out.dim() == 2 && out.size(0) == B && out.size(1) >= 5 && out.size(1) % 2 == 1,
+              "out must be int32 [B, 2 + (k + 1) + k]");
+  const int64_t k = (out.size(1) - 3) / 2;
+  TORCH_CHECK(k >= 1 && k <= 7, "spec tokens k must be in [1, 7]");
+  return k;
+}
+
+void spec_accept(Tensor sampled, Tensor q_start, Tensor drafts, Tensor nd, Tensor rows, Tensor hist, Tensor hist_len,
+                 Tensor out) {
+  const int64_t k = check_spec_state(hist, hist_len, rows, out);
+  check_ids(sampled, "sampled");
+  check_i32(q_start, "q_start");
+  check_i32(drafts, "drafts");
+  check_i32(nd, "nd");
+  const int64_t B = rows.numel();
+  TORCH_CHECK(q_start.numel() == B && nd.numel() == B && drafts.numel() == B * k,
+              "q_start / nd must be int32 [B] and drafts int32 [B, k]");
+  c10::DeviceGuard g(hist.device());
+  mlop::launch_spec_accept((const long*)sampled.data_ptr<int64_t>(), (int)sampled.numel(), q_start.data_ptr<int>(),
+                           drafts.data_ptr<int>(), nd.data_ptr<int>(), rows.data_ptr<int>(), hist.data_ptr<int>(),
+                           hist.size(1), (int)hist.size(1), hist_len.data_ptr<int>(), (int)hist.size(0),
+                           out.data_ptr<int>(), (int)k, (int)B, cur_stream());
+}
+
+void spec_propose(Tensor hist, Tensor hist_len, Tensor rows, Tensor cap, int64_t n_max, int64_t n_min, Tensor out) {
+  const int64_t k = check_spec_state(hist, hist_len, rows, out);
+  check_i32(cap, "cap");
+  TORCH_CHECK(cap.numel() == rows.numel(), "cap must be int32 [B]");
+  TORCH_CHECK(1 <= n_min && n_min <= n_max && n_max <= 8, "n-gram lengths must satisfy 1 <= n_min <= n_max <= 8");
+  c10::DeviceGuard g(hist.device());
+  mlop::launch_spec_propose(hist.data_ptr<int>(), hist.size(1), (int)hist.size(1), hist_len.data_ptr<int>(),
+                            (int)hist.size(0), rows.data_ptr<int>(), cap.data_ptr<int>(), (int)n_max, (int)n_min,
+                            out.data_ptr<int>(), (int)k, (int)rows.numel(), cur_stream());
+}
+
 void apply_penalties(Tensor logits, Tensor table, Tensor slots, Tensor rep, Tensor freq, Tensor pres) {
   check_logits(logits);
   check_table(table);
@@ -1114,6 +1158,10 @@ TORCH_LIBRARY(mlop, m) {
   m.def("apply_penalties(Tensor(a!) logits, Tensor table, Tensor slots, Tensor rep, Tensor freq, "
         "Tensor pres) -> ()");
   m.def("token_logprobs(Tensor(a!) out_lp, Tensor(b!) out_id, Tensor logits, Tensor chosen, Tensor want) -> ()");
+  m.def("spec_accept(Tensor sampled, Tensor q_start, Tensor drafts, Tensor nd, Tensor rows, Tensor(a!) hist, "
+        "Tensor(b!) hist_len, Tensor(c!) out) -> ()");
+  m.def("spec_propose(Tensor hist, Tensor hist_len, Tensor rows, Tensor cap, int n_max, int n_min, "
+        "Tensor(a!) out) -> ()");
   m.def("rmsnorm(Tensor(a!) out, Tensor x, Tensor w, float eps) -> ()");
   m.def("add_rmsnorm(Tensor(a!) out, Tensor(b!) residual, Tensor x, Tensor w, float eps) -> ()");
   m.def("rope_cache(Tensor(a!) q_out, Tensor(b!) k_cache, Tensor(c!) v_cache, Tensor qkv, "
@@ -1172,6 +1220,8 @@ TORCH_LIBRARY_IMPL(mlop, CUDA, m) {
   m.impl("penalty_update", &penalty_update);
   m.impl("apply_penalties", &apply_penalties);
   m.impl("token_logprobs", &token_logprobs);
+  m.impl("spec_accept", &spec_accept);
+  m.impl("spec_propose", &spec_propose);
   m.impl("car_all_reduce", &car_all_reduce);
   m.impl("car_all_reduce_add", &car_all_reduce_add);
   m.impl("car_broadcast", &car_broadcast);

@@ -197,6 +197,13 @@ int logprob_splits(int n, int V);
 long logprob_workspace_bytes(int n, int V);
 void launch_token_logprobs(float* out_lp, int* out_id, int ldo, const void* logits, bool bf16, int n, int V,
                            long ld, const long* chosen, const int* want, void* ws, hipStream_t st);
+// speculative decoding by prompt lookup (spec.hip).  hist int32 [R, ld >= max_len], hist_len [R];
+// out int32 [B, 3 + 2k] = [emitted count, next draft count, k + 1 emitted, k next drafts]
+void launch_spec_accept(const long* sampled, int T, const int* q_start, const int* drafts, const int* nd,
+                        const int* rows, int* hist, long ld, int max_len, int* hist_len, int R, int* out, int k,
+                        int B, hipStream_t st);
+void launch_spec_propose(const int* hist, long ld, int max_len, const int* hist_len, int R, const int* rows,
+                         const int* cap, int n_max, int n_min, int* out, int k, int B, hipStream_t st);
 
 // lazily backed KV arenas (vmm.hip): reserve VA, back chunks synchronously or on a native
 // worker thread; the returned owner must outlive every use of the range

@@ -104,7 +104,8 @@ class MetaBuffers:
     and ``max_seqs`` concurrent sequences."""
 
     def __init__(self, max_tokens: int, max_seqs: int, max_blocks_per_seq: int, group: int,
-                 n_kv: int, max_model_len: int, device, flash_min_q: int = 17, window: int = 0):
+                 n_kv: int, max_model_len: int, device, flash_min_q: int = 17, window: int = 0,
+                 max_logits: int | None = None):
         self.device = torch.device(device)
         self.window = int(window or 0)  # the model's sliding window, stamped into every meta()
         self.max_tokens, self.max_seqs, self.mb = max_tokens, max_seqs, max_blocks_per_seq
@@ -133,7 +134,10 @@ class MetaBuffers:
         ids_lo = o
         o += (2 * max_tokens + 63) // 64 * 64
         lidx_lo = o
-        o += (2 * max_seqs + 63) // 64 * 64
+        # one logits row per sequence; a speculative engine's verify steps have one per TOKEN
+        # (``max_logits``), which only such an engine asks for: the layout is otherwise unchanged
+        n_lidx = max_seqs if max_logits is None else max(max_seqs, max_logits)
+        o += (2 * n_lidx + 63) // 64 * 64
         self.off["block_tables"] = (o, max_seqs * max_blocks_per_seq)
         o += (max_seqs * max_blocks_per_seq + 63) // 64 * 64
         self.total = o
@@ -149,9 +153,9 @@ class MetaBuffers:
         self.ids_h = self.hbuf[ids_lo:ids_lo + 2 * max_tokens].view(torch.int64)
         self.ids_hn = self.ids_h.numpy()
         self.ids_d = self.dbuf[ids_lo:ids_lo + 2 * max_tokens].view(torch.int64)
-        self.lidx_h = self.hbuf[lidx_lo:lidx_lo + 2 * max_seqs].view(torch.int64)
+        self.lidx_h = self.hbuf[lidx_lo:lidx_lo + 2 * n_lidx].view(torch.int64)
         self.lidx_hn = self.lidx_h.numpy()
-        self.lidx_d = self.dbuf[lidx_lo:lidx_lo + 2 * max_seqs].view(torch.int64)
+        self.lidx_d = self.dbuf[lidx_lo:lidx_lo + 2 * n_lidx].view(torch.int64)
         # partial-softmax workspace for the split-KV path (sized for the worst launch)
         # plan_partitions only splits launches with < target/2 base workgroups, so
         # tiles * n_kv * nparts stays <= ~2 * target: size for 4096 partial tiles
@@ -269,6 +273,33 @@ class MetaBuffers:
             order_flash_tiles(pts_h[:npt], ptq_h[:npt], self._pwork[:npt])
         self.npt = npt
         return t, nt, nl
+
+    def fill_verify(self, rows, q_lens, ctx_lens, token_ids_per_seq, pad_tokens: int = 0, pad_tiles: int = 0):
+        """A speculative verify step: row i feeds its last token and its drafts (q_lens[i] = 1 +
+        drafts <= 8 tokens on the 16-row tiles, causal inside the tile), ctx_lens[i] = the context
+        after all of them, and EVERY token gets a logits row (the logits index is the identity).
+        ``pad_tokens`` / ``pad_tiles``: the fixed shape of a captured graph; the token and tile
+        slots the rows leave unused go to the reserved padding rows (slot -1, context 0, up to
+        ``qt`` tokens per padding tile; a tile left over holds none).  Returns (T, tiles, T)."""
+        assert max(q_lens, default=1) < self.flash_min_q
+        t, nt, _ = self._fill_ragged(0, 0, 0, rows, q_lens, ctx_lens, token_ids_per_seq, None)
+        if pad_tokens:
+            T, NT, qt = pad_tokens, pad_tiles, self.qt
+            P, NP = T - t, NT - nt
+            assert P >= 0 and NP >= 0 and NP * qt >= P, "verify graph too small for this step"
+            pad_rows = self.pad_rows(NP)
+            first = np.minimum(np.arange(NP, dtype=np.int32) * qt, P)
+            self.view_h("positions")[t:T] = 0
+            self.view_h("slots")[t:T] = -1
+            self.ids_hn[t:T] = 0
+            self.view_h("tile_seq")[nt:NT] = pad_rows
+            self.view_h("tile_q0")[nt:NT] = 0
+            self.view_h("q_start")[pad_rows] = np.minimum(t + first, T - 1)
+            self.view_h("q_len")[pad_rows] = np.minimum(qt, P - first)
+            self.view_h("ctx_len")[pad_rows] = 0
+            t, nt = T, NT
+        self.lidx_hn[:t] = np.arange(t)
+        return t, nt, t
 
     def fill_decode(self, rows: np.ndarray, ctx_lens: np.ndarray, last_tokens: np.ndarray, pad_to: int):
         """Vectorised decode fill: one query token per sequence, padded to the

@@ -166,6 +166,8 @@ class LLMBackend:
                 m.kv_usage.labels(**m.labels).set(eng.kv_usage())
                 m.kv_blocks.labels(**m.labels).set(eng.alloc.available)
                 m.kv_fill_failed.labels(**m.labels).set(1 if eng.stats.get("kv_fill_failed") else 0)
+                if getattr(eng, "spec_k", 0):
+                    m.mark_spec(eng.stats["spec_drafted"], eng.stats["spec_accepted"])
 
     # ----- asyncio side -----
     def submit(self, prompt_ids, params: SamplingParams, stream: bool = False) -> _Req:

@@ -19,7 +19,12 @@ Step policy:
     eager ragged forward, so decode rides in the prefill's larger-M GEMMs
     instead of stalling behind a separate prefill pass;
   * KV pages come from a free-list; on exhaustion the newest running sequence
-    is preempted (pages freed, recomputed later).
+    is preempted (pages freed, recomputed later);
+  * with ``spec_tokens`` = k > 0 (speculative decoding by prompt lookup, runtime/spec.py) a
+    decode-only step of at most ``spec_max_batch`` rows becomes a VERIFY step when a row has
+    drafts: each row feeds its last token and up to k drafts, every token is sampled, the leading
+    drafts the sampler reproduced are accepted; it replays the verify graph of its bucket.
+    Such an engine steps synchronously.
 """
 from __future__ import annotations
 
@@ -238,6 +243,17 @@ class EngineConfig:
     # 2 D / (D + 1) = 1.98x the pages per byte.  fp8 has no sliding-window, flash-prefill, MoE or
     # fused-epilogue kernels: those models are rejected, prompt chunks run on the 16-row tiles.
     kv_cache_dtype: str = "bf16"
+    # speculative decoding by prompt lookup (runtime/spec.py): up to ``spec_tokens`` (k <= 7) draft
+    # tokens per row, found by matching the sequence's last ``spec_ngram_max`` .. ``spec_ngram_min``
+    # tokens in its own history, are verified in one pass with the row's decode token; outputs are
+    # exactly those of k = 0.  0 = off: nothing is allocated, captured or routed differently.  Such
+    # an engine runs synchronous steps (the host needs the accept counts to place the next step).
+    # Decode steps of more than ``spec_max_batch`` rows run unspeculated: 16 is the largest batch
+    # measured, where 60 % accepted drafts still give 1.4-2.3x (profiles/spec_decode.md)
+    spec_tokens: int = 0
+    spec_ngram_max: int = 3
+    spec_ngram_min: int = 1
+    spec_max_batch: int = 16
 
 
 @dataclass
@@ -271,10 +287,14 @@ class _Step:
     part: engine ``rows`` (int32 [B]) and their context lengths ``ctx_d``.  The prompt part (all
     empty in a decode step): the sequences of ``batch`` with their ``chunks`` (tokens this step),
     ``p_ctx`` (cached length after it), ``done`` (the prompt completes) and ``done_seqs``.  The
-    logits rows are the decode rows, then ``done_seqs``: engine rows ``srows``, sequences ``seqs``."""
+    logits rows are the decode rows, then ``done_seqs``: engine rows ``srows``, sequences ``seqs``.
+
+    A speculative verify step (``nd`` not None) feeds decode row i its last token and ``nd[i]`` of
+    ``drafts[i]``: its ``nlog`` logits rows are the rows' tokens in order, row i's from ``q0[i]``,
+    ``srows`` the engine row and ``goff`` the offset inside its row of each."""
 
     __slots__ = ("rows", "ctx_d", "B", "batch", "chunks", "p_ctx", "done", "done_seqs", "srows", "seqs",
-                 "T", "launch", "params", "greedy")
+                 "T", "launch", "params", "greedy", "nd", "drafts", "q0", "goff", "nlog")
 
 
 class _Pending:
@@ -356,6 +376,12 @@ class Engine:
                 raise ValueError('kv_cache_dtype="fp8" is not supported for MoE models / expert parallelism')
             if mc.head_dim != 128:
                 raise ValueError('kv_cache_dtype="fp8" needs head_dim 128')
+        self.spec_k = int(cfg.spec_tokens or 0)
+        # optional callable (seq, cap) -> list[int]: replaces the device n-gram proposals (the
+        # extension point of a draft-model proposer; lets tests force any acceptance pattern)
+        self.spec_proposer = None
+        if self.spec_k:
+            self._check_spec(cfg, mc, model)
         # multi-LoRA: the slot-major adapter stacks, allocated before the KV pool is sized from
         # what is left (raises for Mixtral / TP > 1 / EP)
         self.lora = None
@@ -392,10 +418,22 @@ class Engine:
         if self.buckets[-1] < cfg.max_num_seqs:
             self.buckets.append(cfg.max_num_seqs)
         self.G = model.n_q // model.n_kv
-        self.meta = MetaBuffers(max(cfg.max_num_batched_tokens, cfg.max_num_seqs),
-                                cfg.max_num_seqs + self.buckets[-1], self.max_blocks_per_seq,
+        max_tokens, pad_rows, spec_kw = max(cfg.max_num_batched_tokens, cfg.max_num_seqs), self.buckets[-1], {}
+        if self.spec_k:
+            # a verify step: up to spec_max_batch rows of k + 1 tokens, a logits row for each.  Its
+            # graph of bucket b has b (k + 1) tokens and b (ceil((k + 1) / qt) + 1) tiles: a row's
+            # own tiles, and one more so that the token slots the rows leave unused always fit
+            # the padding tiles (qt tokens each); every padding tile needs a padding row
+            self.spec_max_batch = max(1, min(cfg.spec_max_batch, cfg.max_num_seqs))
+            qt = max(1, 16 // self.G)
+            self._spec_tpr = (self.spec_k + qt) // qt + 1
+            self.spec_buckets = [b for b in self.buckets if b <= self.spec_max_batch]
+            max_tokens = max(max_tokens, self.spec_max_batch * max(self.spec_k + 1, self._spec_tpr))  # (and tiles)
+            pad_rows = max(pad_rows, max(self.spec_buckets, default=0) * self._spec_tpr)
+            spec_kw = {"max_logits": self.spec_max_batch * (self.spec_k + 1)}
+        self.meta = MetaBuffers(max_tokens, cfg.max_num_seqs + pad_rows, self.max_blocks_per_seq,
                                 self.G, model.n_kv, self.max_model_len, self.device,
-                                window=getattr(mc, "sliding_window", 0),
+                                window=getattr(mc, "sliding_window", 0), **spec_kw,
                                 # fp8 pages have no flash-prefill kernel: every row on the 16-row tiles
                                 # (the route G > 8 takes)
                                 **({"flash_min_q": 1 << 30} if self.fp8_kv else {}))
@@ -458,6 +496,14 @@ class Engine:
         # only the leader schedules (workers follow the host-side headers, StepSync); under EP
         # every rank runs it, the per-step agreement happens at launch time (_ep_agree)
         self._async = cfg.async_scheduling and cfg.mixed_prefill
+        self.graphs_spec: dict[int, tuple] = {}
+        self._step_spec = False  # the step being launched is a verify step
+        if self.spec_k:
+            if self._async:
+                # the host needs a step's accept counts to place the next step's tokens
+                self._async = False
+                self.stats["spec_async_off"] = 1
+            self._spec_init()
         self._pending = None
         self._ids_gather = None
         self._meta_ev = None
@@ -514,6 +560,155 @@ class Engine:
 
         ep.ex = EPExchange(ep.rank, ep.size, mc.num_experts, mc.top_k, mc.hidden_size, self.meta.max_tokens,
                            self.device, group=ep.handle)
+
+    # ------------------------------------------------------ speculation --
+    def _check_spec(self, cfg, mc, model):
+        """ValueError for what a speculative engine does not serve yet (each a follow-up)."""
+        from .spec import MAX_NGRAM, MAX_SPEC_TOKENS
+
+        k = cfg.spec_tokens
+        if not isinstance(k, int) or not 1 <= k <= MAX_SPEC_TOKENS:
+            raise ValueError(f"spec_tokens must be an int in [0, {MAX_SPEC_TOKENS}], got {k!r}")
+        if not 1 <= cfg.spec_ngram_min <= cfg.spec_ngram_max <= MAX_NGRAM:
+            raise ValueError(f"need 1 <= spec_ngram_min <= spec_ngram_max <= {MAX_NGRAM}, got "
+                             f"{cfg.spec_ngram_min} / {cfg.spec_ngram_max}")
+        if cfg.spec_max_batch < 1:
+            raise ValueError(f"spec_max_batch must be >= 1, got {cfg.spec_max_batch}")
+        if model.ps.tp.size > 1 or model.ps.ep.size > 1:
+            raise ValueError("spec_tokens > 0 is not supported with tensor or expert parallelism")
+        if getattr(mc, "is_moe", False):
+            raise ValueError("spec_tokens > 0 is not supported for MoE models")
+        if int(getattr(mc, "sliding_window", 0) or 0) > 0:
+            raise ValueError(f"spec_tokens > 0 is not supported for sliding-window models "
+                             f"(sliding_window = {mc.sliding_window})")
+        if cfg.kv_cache_dtype == "fp8":
+            raise ValueError('spec_tokens > 0 is not supported with kv_cache_dtype="fp8"')
+        if cfg.max_adapters > 0:
+            raise ValueError("spec_tokens > 0 is not supported with LoRA adapters (max_adapters > 0)")
+
+    def _spec_init(self):
+        """The speculative engine's state: every running row's tokens on the device (``hist`` /
+        ``hist_len``, written by ops.spec_accept), the per-step arguments of the two kernels in
+        ONE pinned buffer (one H2D) and their result (one D2H), and each row's next drafts."""
+        from .spec import out_width
+
+        R, k, dev = self.cfg.max_num_seqs, self.spec_k, self.device
+        cuda = dev.type == "cuda"
+        self.hist = torch.zeros(R, self.max_model_len, dtype=torch.int32, device=dev)
+        self.hist_len = torch.zeros(R, dtype=torch.int32, device=dev)
+        W = self._spec_w = out_width(k)
+        self._spec_arg_h = torch.zeros(R * (4 + k), dtype=torch.int32, pin_memory=cuda)
+        self._spec_arg_d = torch.zeros(R * (4 + k), dtype=torch.int32, device=dev)
+        self._spec_out_d = torch.zeros(R, W, dtype=torch.int32, device=dev)
+        self._spec_out_h = torch.zeros(R, W, dtype=torch.int32, pin_memory=cuda)
+        self.r_nd = np.zeros(R, np.int64)            # the row's drafts for its next step
+        self.r_drafts = np.zeros((R, k), np.int64)
+        self.r_ext = np.zeros(R, bool)               # on the sampler's extended path: never drafts
+        self.stats["spec_hist_bytes"] = self.hist.numel() * 4
+        for key in ("spec_steps", "spec_graph_steps", "spec_drafted", "spec_accepted"):
+            self.stats[key] = 0
+
+    def _hist_load(self, s: Sequence) -> None:
+        """A sequence is about to join the running rows (its prompt completes in the step being
+        launched, re-admission after preemption included): its tokens so far go to hist[row], on
+        the engine's stream; the step's spec_accept appends its first token behind them."""
+        n = s.length
+        self.hist[s.row, :n].copy_(torch.tensor(s.prompt + s.output, dtype=torch.int32))
+        self.hist_len[s.row:s.row + 1].fill_(n)
+        self.r_nd[s.row] = 0
+        self.r_ext[s.row] = s.params.extended
+
+    def _spec_drafts(self, rows):
+        """Draft counts and drafts (int64 [B], [B, k]) of a decode-only step over ``rows``, or None:
+        no row has any.  A row's cap is min(k, tokens it may still generate - 1, positions left -
+        1), 0 on the sampler's extended path (penalties / log-probabilities: the draw depends on
+        the previous token's table update).  The pages up to len + drafts are ensured; a row the
+        allocator cannot serve drops its drafts (nothing is preempted for a draft)."""
+        k = self.spec_k
+        left = np.minimum(self.r_maxgen[rows] - self.r_gen[rows], self.max_model_len - self.r_len[rows]) - 1
+        cap = np.where(self.r_ext[rows], 0, np.clip(left, 0, k))
+        if self.spec_proposer is not None:
+            nd, drafts = np.zeros(len(rows), np.int64), np.zeros((len(rows), k), np.int64)
+            V = self.model.cfg.vocab_size
+            for i in np.nonzero(cap)[0].tolist():
+                d = [int(t) for t in self.spec_proposer(self.running[i], int(cap[i]))][:int(cap[i])]
+                bad = next((j for j, t in enumerate(d) if not 0 <= t < V), len(d))
+                nd[i] = bad
+                drafts[i, :bad] = d[:bad]
+        else:
+            nd, drafts = np.minimum(self.r_nd[rows], cap), self.r_drafts[rows]
+        for i in np.nonzero(nd)[0].tolist():
+            if not self._ensure_blocks(self.running[i], int(self.r_len[rows[i]] + nd[i])):
+                nd[i] = 0
+        return (nd, drafts) if nd.any() else None
+
+    def _spec_post(self, st: _Step, toks_d):
+        """Behind a step's draw, on the same stream: ops.spec_accept over its logits sequences (the
+        decode rows, then the completed prompts; plain rows have no drafts), ops.spec_propose for
+        their next step, and ONE read-back of both: int32 [n, 2 + (k + 1) + k] (NumPy)."""
+        k, B = self.spec_k, st.B
+        arows = self._sample_rows(st.rows, st.done_seqs)
+        n = len(arows)
+        a = self._spec_arg_h.numpy()
+        q0, nd, rw, cap = (a[i * n:(i + 1) * n] for i in range(4))  # [q_start | nd | rows | cap | drafts]
+        dr = a[4 * n:(4 + k) * n].reshape(n, k)
+        q0[:] = np.arange(n)
+        nd[:] = 0
+        dr[:] = 0
+        if st.nd is not None:
+            q0[:B], nd[:B], dr[:B] = st.q0, st.nd, st.drafts
+            q0[B:] = st.nlog + np.arange(n - B)
+        rw[:] = arows
+        cap[:] = np.where(self.r_ext[arows], 0, k)
+        m = (4 + k) * n
+        ad = self._spec_arg_d
+        ad[:m].copy_(self._spec_arg_h[:m], non_blocking=True)
+        out_d = self._spec_out_d[:n]
+        ops.spec_accept(toks_d, ad[:n], ad[4 * n:m].view(n, k), ad[n:2 * n], ad[2 * n:3 * n], self.hist,
+                        self.hist_len, out_d)
+        if self.spec_proposer is None:
+            ops.spec_propose(self.hist, self.hist_len, ad[2 * n:3 * n], ad[3 * n:4 * n], self.cfg.spec_ngram_max,
+                             self.cfg.spec_ngram_min, out_d)
+        if self.device.type != "cuda":
+            return out_d.numpy(), arows
+        out_h = self._spec_out_h[:n]
+        out_h.copy_(out_d, non_blocking=True)
+        torch.cuda.current_stream(self.device).synchronize()
+        return out_h.numpy(), arows
+
+    def _spec_finish(self, rows, cnt, emitted, lp=None) -> StepBatch:
+        """Bookkeeping of a verify step: running row i emitted ``emitted[i, :cnt[i]]``.  Stop
+        tokens and EOS are applied in order: emission ends at the first one and the sequence
+        finishes there."""
+        run, eos = self.running, self.model.cfg.eos_ids
+        n = len(rows)
+        m = np.zeros(n, np.int64)
+        last = np.zeros(n, np.int64)
+        fin_stop = np.zeros(n, bool)
+        toks = []
+        for i, (s, c) in enumerate(zip(run, cnt.tolist())):
+            t = emitted[i, :c].tolist()
+            r = rows[i]
+            stops = s.params.stop_token_ids if self.r_hasstop[r] else ()
+            for j, tok in enumerate(t):
+                if (not self.r_ignore[r] and tok in eos) or tok in stops:
+                    t, fin_stop[i] = t[:j + 1], True
+                    break
+            s.output.extend(t)
+            toks.extend(t)
+            m[i], last[i] = len(t), t[-1]
+        self.r_len[rows] += m
+        self.r_gen[rows] += m
+        self.r_last[rows] = last
+        self.stats["decode_tokens"] += int(m.sum()) - n
+        fin_len = (self.r_gen[rows] >= self.r_maxgen[rows]) | (self.r_len[rows] >= self.max_model_len)
+        fin = fin_stop | fin_len
+        lps = self._deliver_lp(run, lp, self.r_want[rows]) if lp is not None else None
+        sids = np.repeat(self.r_sid[rows], m)
+        fin_t = np.zeros(len(toks), bool)
+        fin_t[np.cumsum(m) - 1] = fin  # a sequence finishes with its last emitted token
+        reasons = self._retire_rows(rows, fin, fin_stop)
+        return StepBatch(sids, np.asarray(toks, dtype=np.int64), fin_t, reasons, lps)
 
     # ----------------------------------------------------------- sizing --
     def _auto_blocks(self) -> int:
@@ -908,7 +1103,27 @@ class Engine:
         done_seqs = [s for s, d in zip(batch, done) if d]
         last = ids[rows]
         mctx = max(int(ctx_d.max()) if B else 0, max(p_ctx, default=0))
-        if batch:
+        st.nd = st.drafts = st.q0 = st.goff = None
+        spec = self._spec_drafts(rows) if (self.spec_k and B and not batch and B <= self.spec_max_batch) else None
+        self._step_spec = spec is not None
+        if spec is not None:
+            # a verify step: row i's last token and its drafts, causal inside the row, a logits
+            # row for every token; replays the verify graph of the bucket where one was captured
+            k = self.spec_k
+            st.nd, st.drafts = nd, drafts = spec
+            q_lens = 1 + nd
+            st.q0 = np.cumsum(q_lens) - q_lens
+            toks = [[int(last[i]), *drafts[i, :nd[i]].tolist()] for i in range(B)]
+            bucket = next((b for b in self.buckets if b >= B), None)
+            pad = {}
+            if self.graphs_spec.get(bucket) is not None:
+                pad = {"pad_tokens": bucket * (k + 1), "pad_tiles": bucket * self._spec_tpr}
+            T, nt, nl = meta.fill_verify(rows, q_lens, ctx_d + nd.astype(np.int32), toks, **pad)
+            if pad:
+                st.launch = (KIND_GRAPH, T, nt, nl, 0, 0, bucket)
+            else:
+                st.launch = (KIND_EAGER, T, nt, nl, *plan_partitions(nt, n_kv, meta.span(mctx + k)), 0)
+        elif batch:
             T, nt, nl = meta.fill_mixed(rows, ctx_d, last, [s.row for s in batch], chunks, p_ctx,
                                         [s.tokens(s.num_cached, c) for s, c in zip(batch, p_ctx)], want_logits=done)
             st.launch = (KIND_EAGER, T, nt, nl, *plan_partitions(nt, n_kv, meta.span(mctx)), 0)
@@ -930,6 +1145,14 @@ class Engine:
             st.params = _ParamsList([s.params for s in (self.running if decode else ())] + [s.params for s in done_seqs])
         st.greedy = st.params is _ALL_GREEDY
         st.rows, st.ctx_d, st.B, st.srows = rows, ctx_d, B, self._sample_rows(rows, done_seqs)
+        st.nlog = B + len(done_seqs)
+        if spec is not None:
+            # one draw per token: the row's own params repeated, output positions consecutive
+            st.nlog = int(q_lens.sum())
+            st.srows = np.repeat(rows, q_lens)
+            st.goff = np.arange(st.nlog) - np.repeat(st.q0, q_lens)
+            if not st.greedy:
+                st.params = _ParamsList([s.params for s, q in zip(self.running, q_lens.tolist()) for _ in range(q)])
         st.batch, st.chunks, st.p_ctx, st.done, st.done_seqs = batch, chunks, p_ctx, done, done_seqs
         return st
 
@@ -947,11 +1170,19 @@ class Engine:
             self.stats["decode_steps"] += 1
         if B:
             self.stats["decode_tokens"] += B
+        if st.nd is not None:
+            self.stats["spec_steps"] += 1
+            self.stats["spec_graph_steps"] += int(st.launch[0] == KIND_GRAPH)
+            self.stats["spec_drafted"] += int(st.nd.sum())
         if logits is None:
             return None, None
         if st.launch[0] == KIND_GRAPH:
-            logits = logits[:B]  # (its padding rows)
-        toks_d = self._sample(logits, st.params, lambda: self._gen_index(st.rows, st.done_seqs), st.srows)
+            logits = logits[:st.nlog]  # (its padding rows)
+        if st.nd is not None:
+            gen_index = lambda: self.r_gen[st.srows] + st.goff  # noqa: E731
+        else:
+            gen_index = lambda: self._gen_index(st.rows, st.done_seqs)  # noqa: E731
+        toks_d = self._sample(logits, st.params, gen_index, st.srows)
         lp_d, self._last_lp = self._last_lp, None
         return toks_d, lp_d
 
@@ -963,16 +1194,36 @@ class Engine:
         if st is None:
             return None
         t1 = time.perf_counter()
+        if self.spec_k:
+            for s in st.done_seqs:
+                self._hist_load(s)
         toks_d, lp_d = self._issue(st)
-        toks = lp = None
-        if toks_d is not None:
+        toks = lp = res = None
+        if toks_d is not None and self.spec_k:
+            # every sampled token of a speculative engine goes through spec_accept (the history
+            # holds every token of a running row); the tokens come back with the accept counts
+            # and the rows' next drafts in one read
+            res, arows = self._spec_post(st, toks_d)
+            toks = res[:, 2].astype(np.int64)
+            if self.spec_proposer is None:
+                self.r_nd[arows], self.r_drafts[arows] = res[:, 1], res[:, 3 + self.spec_k:]
+            if lp_d is not None:
+                lp = (lp_d[0].cpu().numpy(), lp_d[1].cpu().numpy())
+                if st.nd is not None:  # per token -> per row (such a row has no drafts)
+                    lp = (lp[0][st.q0], lp[1][st.q0])
+        elif toks_d is not None:
             toks = toks_d.cpu().numpy().astype(np.int64)
             lp = None if lp_d is None else (lp_d[0].cpu().numpy(), lp_d[1].cpu().numpy())
         elif self.device.type == "cuda":
             torch.cuda.synchronize()
         t2 = time.perf_counter()
         B = st.B
-        out = self._decode_finish(st.rows, toks[:B], lp) if B else None
+        if st.nd is not None:
+            self.stats["spec_accepted"] += int(res[:B, 0].sum()) - B
+        if st.nd is not None and (res[:B, 0] != 1).any():
+            out = self._spec_finish(st.rows, res[:B, 0], res[:B, 2:3 + self.spec_k], lp)
+        else:
+            out = self._decode_finish(st.rows, toks[:B], lp) if B else None
         if st.batch:
             p_out = self._chunks_done(st, [] if toks is None else toks[B:].tolist(), lp)
             if out is None or p_out:
@@ -1356,6 +1607,12 @@ class Engine:
         collections.deque(map(list.append, self._outs, toks.tolist()), maxlen=0)
         lps = self._deliver_lp(run, lp, self.r_want[rows]) if lp is not None else None
         sids = self.r_sid[rows].copy()
+        return StepBatch(sids, toks, fin, self._retire_rows(rows, fin, fin_stop), lps)
+
+    def _retire_rows(self, rows, fin, fin_stop) -> dict:
+        """The running rows flagged in ``fin`` finish ("stop" where ``fin_stop``, else "length") and
+        leave the running set; returns seq_id -> reason."""
+        run = self.running
         reasons = {}
         fi = np.nonzero(fin)[0]
         if len(fi):
@@ -1365,7 +1622,7 @@ class Engine:
             self._keep_running(rows, np.nonzero(~fin)[0])
             for s in done:
                 self._finish(s, reasons[s.seq_id])
-        return StepBatch(sids, toks, fin, reasons, lps)
+        return reasons
 
     def _append(self, s: Sequence, tok: int) -> StepOutput:
         s.output.append(int(tok))
@@ -1445,7 +1702,8 @@ class Engine:
         if lora:
             self.stats["lora_steps"] += 1
         if kind == KIND_GRAPH:
-            graph, logits_buf = (self.graphs_lora if lora else self.graphs)[bucket]
+            family = self.graphs_spec if self._step_spec else self.graphs_lora if lora else self.graphs
+            graph, logits_buf = family[bucket]
             graph.replay()
             if lora:
                 self.stats["lora_graph_steps"] += 1
@@ -1580,6 +1838,18 @@ class Engine:
                     m.logits_local(m.forward(ids, meta, self.kv, lora=step))
                     stream.synchronize()
                     self.graphs_lora[b] = capture(lora=step)
+            for b in sorted(self.spec_buckets if self.spec_k else (), reverse=True):
+                # third family: the verify step of bucket b, b (k + 1) tokens with a logits row
+                # each (identity index, as above); captured on padding rows only
+                T, nt, _ = self.meta.fill_verify(empty, empty, empty, [], pad_tokens=b * (self.spec_k + 1),
+                                                 pad_tiles=b * self._spec_tpr)
+                self.meta.upload(T, T)
+                part, nparts = plan_partitions(nt, m.n_kv, self.meta.span(self.max_model_len))
+                meta = self.meta.meta(T, nt, T, part, nparts)
+                ids = self.meta.ids_d[:T]
+                m.logits_local(m.forward(ids, meta, self.kv))
+                stream.synchronize()
+                self.graphs_spec[b] = capture()
         torch.cuda.current_stream(self.device).wait_stream(stream)
         torch.cuda.synchronize(self.device)
         self.stats["graph_capture_ms"] = int(1e3 * (time.perf_counter() - t0))

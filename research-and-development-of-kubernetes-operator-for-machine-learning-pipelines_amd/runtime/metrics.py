@@ -87,6 +87,13 @@ class RuntimeMetrics:
         self.gpu_power = Gauge("mlop_gpu_power_watts", "Socket power", base + ["gpu"], registry=r)
         self.engine_steps = Counter("mlop_engine_steps", "Engine steps executed", base, registry=r)
         self.engine_tokens = Counter("mlop_engine_tokens", "Tokens emitted by engine steps", base, registry=r)
+        # speculative decoding (EngineConfig.spec_tokens > 0; exposed as ..._total): drafts fed to verify
+        # steps and drafts the sampler reproduced; their ratio is the acceptance rate
+        self.spec_drafted = Counter("mlop_spec_draft_tokens", "Draft tokens verified by speculative steps", base,
+                                    registry=r)
+        self.spec_accepted = Counter("mlop_spec_accepted_tokens", "Draft tokens accepted by speculative steps", base,
+                                     registry=r)
+        self._spec_seen = (0, 0)
         # the engine thread's perf_counter at the end of its last step AND the token total at that
         # instant, exported from ONE snapshot (``mark_step``): a rate over two scrapes then needs
         # no client-side clock (the scrape's own latency on a busy event loop skewed a 2-3 s
@@ -105,6 +112,15 @@ class RuntimeMetrics:
             self.engine_tokens.labels(**self.labels).inc(tokens)
         self._tok_total += tokens
         self._clock.snap = (self._tok_total, now)  # one reference store: scrapes see a consistent pair
+
+    def mark_spec(self, drafted: int, accepted: int) -> None:
+        """Engine thread: the engine's running totals (Engine.stats) -> the two counters."""
+        d0, a0 = self._spec_seen
+        if drafted > d0:
+            self.spec_drafted.labels(**self.labels).inc(drafted - d0)
+        if accepted > a0:
+            self.spec_accepted.labels(**self.labels).inc(accepted - a0)
+        self._spec_seen = (max(d0, drafted), max(a0, accepted))
 
     def lv(self, **extra):
         return dict(self.labels, **extra)
