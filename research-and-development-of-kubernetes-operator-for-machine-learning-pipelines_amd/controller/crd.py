@@ -88,6 +88,7 @@ class CanaryPolicy:
 
 KV_CACHE_DTYPES = ("bf16", "fp8")  # spec.kvCacheDtype (manifests/crd.yaml's enum)
 MAX_SPECULATIVE_TOKENS = 7         # spec.speculativeTokens (manifests/crd.yaml's maximum; runtime/spec.py)
+MAX_GUIDED_STATES = 32767          # spec.guidedDecodingStates (int16 arena entries; runtime/guided.py)
 
 
 @dataclass(frozen=True)
@@ -111,6 +112,8 @@ class ModelSpec:
     kv_cache_dtype: str | None = None
     # draft tokens per step of the LLM runtime's prompt-lookup speculative decoding: None / 0 = off, 1..7
     speculative_tokens: int | None = None
+    # rows of the LLM runtime's guided-decoding grammar arena: None / 0 = off, up to 32767
+    guided_decoding_states: int | None = None
 
     @classmethod
     def from_spec(cls, spec: dict) -> "ModelSpec":
@@ -128,7 +131,8 @@ class ModelSpec:
                    adapters=tuple((a.get("name"), a.get("uri")) for a in (spec.get("adapters") or [])
                                   if isinstance(a, dict)),
                    kv_cache_dtype=spec.get("kvCacheDtype"),
-                   speculative_tokens=spec.get("speculativeTokens"))
+                   speculative_tokens=spec.get("speculativeTokens"),
+                   guided_decoding_states=spec.get("guidedDecodingStates"))
 
     def validate(self) -> list[str]:
         errs = []
@@ -163,6 +167,12 @@ class ModelSpec:
                     errs.append("spec.speculativeTokens is not supported with kvCacheDtype fp8")
                 if self.adapters:
                     errs.append("spec.speculativeTokens is not supported with adapters")
+        g = self.guided_decoding_states
+        if g is not None:
+            if isinstance(g, bool) or not isinstance(g, int) or not 0 <= g <= MAX_GUIDED_STATES:
+                errs.append(f"spec.guidedDecodingStates must be an integer in [0, {MAX_GUIDED_STATES}], not {g!r}")
+            elif g > 0 and (int(self.tensor_parallel or 1) > 1 or int(self.expert_parallel or 1) > 1):
+                errs.append("spec.guidedDecodingStates needs tensorParallel = 1 and expertParallel = 1")
         return errs
 
 

@@ -47,14 +47,15 @@ def plan(arch: str | ModelConfig, max_model_len: int = 4096, max_num_seqs: int =
          hbm_gb: float = 288.0, gpus_per_node: int = 8, utilization: float = 0.90,
          reserve_gb: float = 8.0, requested_tp: int | None = None, requested_ep: int | None = None,
          kv_target_fraction: float = 0.5, free_gpus: int | None = None,
-         kv_cache_dtype: str | None = None) -> Placement:
+         kv_cache_dtype: str | None = None, grammar_states: int = 0) -> Placement:
     """``free_gpus``: GPUs the target node still has unallocated (reconciler.node_capacity);
     a placement needing more is returned with ``fits=False`` and the reason (the pod would
     stay Pending), whatever its HBM arithmetic says.  ``kv_cache_dtype`` ("bf16" / "fp8"): the
     engine's KV cache format; the KV target and capacity use its bytes per token, scale bytes
-    included (None: bf16)."""
+    included (None: bf16).  ``grammar_states``: rows of the guided-decoding arena (int16
+    [states, vocab]), charged states x vocab x 2 bytes beside the weights."""
     p = _plan(arch, max_model_len, max_num_seqs, hbm_gb, gpus_per_node, utilization, reserve_gb,
-              requested_tp, requested_ep, kv_target_fraction, kv_cache_dtype)
+              requested_tp, requested_ep, kv_target_fraction, kv_cache_dtype, grammar_states)
     if free_gpus is not None and p.gpus > free_gpus:
         p.fits = False
         p.reason = (f"needs {p.gpus} GPUs (TP={p.tensorParallel}), the node has {free_gpus} of "
@@ -63,24 +64,25 @@ def plan(arch: str | ModelConfig, max_model_len: int = 4096, max_num_seqs: int =
 
 
 def _plan(arch, max_model_len, max_num_seqs, hbm_gb, gpus_per_node, utilization, reserve_gb, requested_tp,
-          requested_ep, kv_target_fraction, kv_cache_dtype=None) -> Placement:
+          requested_ep, kv_target_fraction, kv_cache_dtype=None, grammar_states=0) -> Placement:
     cfg = arch if isinstance(arch, ModelConfig) else get_config(arch)
     usable = hbm_gb * utilization
     wbytes = cfg.weight_bytes()
     kv_tok = cfg.kv_bytes_per_token(kv_cache_dtype=kv_cache_dtype or "bf16")
     kv_target = max_num_seqs * max_model_len * kv_tok * kv_target_fraction
+    arena = int(grammar_states or 0) * cfg.vocab_size * 2  # guided decoding: int16 [states, vocab]
 
     def evaluate(tp: int, ep: int) -> Placement:
         shards = max(tp, ep)
         w = wbytes / shards
         kv_split = min(tp, cfg.num_kv_heads)  # kv heads replicate beyond Hkv
         kv_per_gpu = kv_target / kv_split
-        free = usable * GB - reserve_gb * GB - w
+        free = usable * GB - reserve_gb * GB - w - arena
         cap = int(max(0.0, free) * kv_split / kv_tok)
         fits = free >= kv_per_gpu
         return Placement(cfg.name, tp, ep, shards, round(w / GB, 2), round(max(0.0, free) / GB, 2), cap,
                          hbm_gb, fits, "" if fits else
-                         f"needs {round((w + kv_per_gpu) / GB + reserve_gb, 1)} GB/GPU > {round(usable, 1)}")
+                         f"needs {round((w + arena + kv_per_gpu) / GB + reserve_gb, 1)} GB/GPU > {round(usable, 1)}")
 
     if requested_tp:
         if not _valid_tp(cfg, requested_tp) or requested_tp > gpus_per_node:

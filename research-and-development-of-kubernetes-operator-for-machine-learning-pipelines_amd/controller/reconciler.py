@@ -207,7 +207,8 @@ class MlflowModelReconciler:
                 f"|len={spec.max_model_len or 4096}|seqs={spec.max_num_seqs or 256}"
                 f"|kvf={spec.kv_target_fraction or 0.5}|replicas={spec.replicas}"
                 # (appended only when set: CRs without the field keep the key their deployed predictors carry)
-                + (f"|kv={spec.kv_cache_dtype}" if spec.kv_cache_dtype else ""))
+                + (f"|kv={spec.kv_cache_dtype}" if spec.kv_cache_dtype else "")
+                + (f"|gs={spec.guided_decoding_states}" if spec.guided_decoding_states else ""))
 
     async def desired_sd(self, body: dict, spec: ModelSpec, status: dict) -> dict | None:
         """The SeldonDeployment this CR wants now.  Placement is decided ONCE per version, like
@@ -259,7 +260,8 @@ class MlflowModelReconciler:
                              gpus_per_node=node.get("gpus", self.settings.gpus_per_node),
                              requested_tp=spec.tensor_parallel, requested_ep=spec.expert_parallel,
                              kv_target_fraction=spec.kv_target_fraction or 0.5,
-                             free_gpus=node.get("free_gpus"), kv_cache_dtype=spec.kv_cache_dtype)
+                             free_gpus=node.get("free_gpus"), kv_cache_dtype=spec.kv_cache_dtype,
+                             grammar_states=spec.guided_decoding_states or 0)
                     placement = {"tensorParallel": p.tensorParallel, "expertParallel": p.expertParallel,
                                  "gpus": p.gpus, "weightGBPerGPU": p.weightGBPerGPU,
                                  "kvTokenCapacity": p.kvTokenCapacity, "fits": p.fits, "placementKey": key}
@@ -288,6 +290,8 @@ class MlflowModelReconciler:
                 engine_args["kv_cache_dtype"] = spec.kv_cache_dtype  # -> MLOP_ENGINE_KV_CACHE_DTYPE
             if spec.speculative_tokens and runtime == seldon.RUNTIME_LLM:
                 engine_args["spec_tokens"] = spec.speculative_tokens  # -> MLOP_ENGINE_SPEC_TOKENS
+            if spec.guided_decoding_states and runtime == seldon.RUNTIME_LLM:
+                engine_args["grammar_states"] = spec.guided_decoding_states  # -> MLOP_ENGINE_GRAMMAR_STATES
             preds.append(seldon.build_predictor(
                 v, uri, spec.minio_secret, traffic, runtime=runtime, replicas=spec.replicas, placement=placement,
                 image=self.settings.runtime_image, gpu_resource=self.settings.gpu_resource,

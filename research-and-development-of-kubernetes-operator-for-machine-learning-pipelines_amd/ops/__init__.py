@@ -818,6 +818,38 @@ def apply_penalties(logits: torch.Tensor, table: torch.Tensor, slots, rep, freq,
     return logits
 
 
+def grammar_arena(states: int, vocab: int, device) -> torch.Tensor:
+    """The guided-decoding arena, int16 [states, ldv] filled with -1 (nothing allowed); ldv = vocab
+    rounded up to 8 so every row starts on a 16-B boundary (runtime/guided.py ``Grammar.next``)."""
+    return torch.full((states, (vocab + 7) // 8 * 8), -1, dtype=torch.int16, device=device)
+
+
+def grammar_mask(logits: torch.Tensor, arena: torch.Tensor, base, rows, state) -> torch.Tensor:
+    """In place on fp32 ``logits`` [n, V]: row i with base[i] >= 0 gets -inf wherever
+    arena[base[i] + state[rows[i]], v] < 0; rows with base[i] < 0 are not read or written."""
+    if not logits.is_cuda:
+        from ..runtime.guided import mask_reference
+
+        return mask_reference(logits, arena, base, state, rows)
+    _need_gpu()
+    torch.ops.mlop.grammar_mask(logits, arena, base, rows, state)
+    return logits
+
+
+def grammar_advance(arena: torch.Tensor, base, rows, state: torch.Tensor, tokens: torch.Tensor,
+                    vocab: int | None = None) -> None:
+    """After the draw: state[rows[i]] = arena[base[i] + state[rows[i]], clamp(tokens[i], 0, V - 1)]
+    for every row with base[i] >= 0, unless that entry is < 0 (then the state stays)."""
+    vocab = arena.shape[1] if vocab is None else vocab
+    if not arena.is_cuda:
+        from ..runtime.guided import advance_reference
+
+        advance_reference(arena, base, state, tokens, rows, vocab)
+        return
+    _need_gpu()
+    torch.ops.mlop.grammar_advance(arena, int(vocab), base, rows, state, tokens.contiguous())
+
+
 def token_logprobs(out_lp: torch.Tensor, out_id: torch.Tensor, logits: torch.Tensor, chosen: torch.Tensor,
                    want: torch.Tensor) -> None:
     """Row i with want[i] = N >= 0: out[i, 0] = (chosen[i], its log-softmax over the whole row),
@@ -859,7 +891,7 @@ def spec_propose(hist, hist_len, rows, cap, n_max: int, n_min: int, out) -> None
 
 
 __all__ = ["argmax", "sample", "penalty_table", "penalty_reset", "penalty_update", "apply_penalties",
-           "token_logprobs", "spec_accept", "spec_propose", "load","available", "library_path", "rmsnorm", "add_rmsnorm", "rope_cache",
+           "token_logprobs", "grammar_arena", "grammar_mask", "grammar_advance", "spec_accept", "spec_propose", "load","available", "library_path", "rmsnorm", "add_rmsnorm", "rope_cache",
            "silu_mul", "embedding", "paged_attention", "ref"]
 
 

@@ -5,6 +5,7 @@
 // HIP stream (so it is hipGraph-capturable) and mutates pre-allocated outputs
 // (cdna_hip_programming.md Guideline 9; the one scratch tensor, gemm_rope_cache's V staging,
 // comes from PyTorch's caching allocator, which serves captures from the graph's pool).
+#include <climits>
 #include <cstdlib>
 #include <string>
 #include <torch/library.h>
@@ -888,6 +889,42 @@ void apply_penalties(Tensor logits, Tensor table, Tensor slots, Tensor rep, Tens
                                rep.data_ptr<float>(), freq.data_ptr<float>(), pres.data_ptr<float>(), cur_stream());
 }
 
+// ---- guided decoding (guided.hip) ----
+void check_grammar(const Tensor& arena, const Tensor& base, const Tensor& rows, const Tensor& state, int64_t n) {
+  TORCH_CHECK(arena.is_cuda() && arena.scalar_type() == at::kShort && arena.is_contiguous() && arena.dim() == 2 &&
+                  arena.size(1) % 8 == 0 && reinterpret_cast<uintptr_t>(arena.data_ptr()) % 16 == 0,
+              "grammar arena must be a contiguous int16 [states, ldv] GPU tensor with ldv % 8 == 0, 16-B aligned");
+  check_i32(base, "base");
+  check_i32(rows, "rows");
+  check_i32(state, "state");
+  TORCH_CHECK(base.numel() == n && rows.numel() == n, "base / rows must be int32 [n]");
+  TORCH_CHECK(arena.size(0) <= INT_MAX && state.numel() <= INT_MAX, "grammar arena / state too large");
+}
+
+void grammar_mask(Tensor logits, Tensor arena, Tensor base, Tensor rows, Tensor state) {
+  TORCH_CHECK(logits.is_cuda() && logits.scalar_type() == at::kFloat && logits.dim() == 2 && logits.stride(1) == 1 &&
+                  (logits.size(0) <= 1 || logits.stride(0) >= logits.size(1)),
+              "logits must be f32 [n, V] with unit inner stride and rows that do not overlap");
+  const int64_t n = logits.size(0);
+  check_grammar(arena, base, rows, state, n);
+  TORCH_CHECK(logits.size(1) <= arena.size(1), "the arena's rows are shorter than the vocabulary");
+  c10::DeviceGuard g(logits.device());
+  mlop::launch_grammar_mask(logits.data_ptr<float>(), (int)n, (int)logits.size(1), logits.stride(0),
+                            (const short*)arena.data_ptr<int16_t>(), arena.size(1), (int)arena.size(0),
+                            base.data_ptr<int>(), rows.data_ptr<int>(), state.data_ptr<int>(), (int)state.numel(),
+                            cur_stream());
+}
+
+void grammar_advance(Tensor arena, int64_t vocab, Tensor base, Tensor rows, Tensor state, Tensor tokens) {
+  check_ids(tokens, "tokens");
+  check_grammar(arena, base, rows, state, tokens.numel());
+  TORCH_CHECK(vocab > 0 && vocab <= arena.size(1), "vocab must be in (0, ldv]");
+  c10::DeviceGuard g(arena.device());
+  mlop::launch_grammar_advance((const short*)arena.data_ptr<int16_t>(), arena.size(1), (int)arena.size(0), (int)vocab,
+                               base.data_ptr<int>(), rows.data_ptr<int>(), state.data_ptr<int>(), (int)state.numel(),
+                               (const long*)tokens.data_ptr<int64_t>(), (int)tokens.numel(), cur_stream());
+}
+
 void token_logprobs(Tensor out_lp, Tensor out_id, Tensor logits, Tensor chosen, Tensor want) {
   const bool bf = logits.scalar_type() == at::kBFloat16;
   if (bf) {
@@ -1155,6 +1192,8 @@ TORCH_LIBRARY(mlop, m) {
         "Tensor uniform, bool full) -> ()");
   m.def("penalty_reset(Tensor(a!) table, int slot, int vocab, Tensor prompt_ids, Tensor output_ids) -> ()");
   m.def("penalty_update(Tensor(a!) table, int vocab, Tensor slots, Tensor tokens) -> ()");
+  m.def("grammar_mask(Tensor(a!) logits, Tensor arena, Tensor base, Tensor rows, Tensor state) -> ()");
+  m.def("grammar_advance(Tensor arena, int vocab, Tensor base, Tensor rows, Tensor(a!) state, Tensor tokens) -> ()");
   m.def("apply_penalties(Tensor(a!) logits, Tensor table, Tensor slots, Tensor rep, Tensor freq, "
         "Tensor pres) -> ()");
   m.def("token_logprobs(Tensor(a!) out_lp, Tensor(b!) out_id, Tensor logits, Tensor chosen, Tensor want) -> ()");
@@ -1218,6 +1257,8 @@ TORCH_LIBRARY_IMPL(mlop, CUDA, m) {
   m.impl("sample", &sample);
   m.impl("penalty_reset", &penalty_reset);
   m.impl("penalty_update", &penalty_update);
+  m.impl("grammar_mask", &grammar_mask);
+  m.impl("grammar_advance", &grammar_advance);
   m.impl("apply_penalties", &apply_penalties);
   m.impl("token_logprobs", &token_logprobs);
   m.impl("spec_accept", &spec_accept);

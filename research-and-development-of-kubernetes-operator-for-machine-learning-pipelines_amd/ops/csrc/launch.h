@@ -197,6 +197,12 @@ int logprob_splits(int n, int V);
 long logprob_workspace_bytes(int n, int V);
 void launch_token_logprobs(float* out_lp, int* out_id, int ldo, const void* logits, bool bf16, int n, int V,
                            long ld, const long* chosen, const int* want, void* ws, hipStream_t st);
+// guided decoding (guided.hip).  Arena int16 [A, ldv >= V] (ldv % 8 == 0): entry [base + s, t] = the
+// grammar's state after token t in state s, < 0 = not allowed; state int32 [R] by engine row
+void launch_grammar_mask(float* logits, int n, int V, long ld, const short* arena, long ldv, int A,
+                         const int* base, const int* rows, const int* state, int R, hipStream_t st);
+void launch_grammar_advance(const short* arena, long ldv, int A, int V, const int* base, const int* rows,
+                            int* state, int R, const long* tokens, int n, hipStream_t st);
 // speculative decoding by prompt lookup (spec.hip).  hist int32 [R, ld >= max_len], hist_len [R];
 // out int32 [B, 3 + 2k] = [emitted count, next draft count, k + 1 emitted, k next drafts]
 void launch_spec_accept(const long* sampled, int T, const int* q_start, const int* drafts, const int* nd,

@@ -385,6 +385,10 @@ __global__ void __launch_bounds__(kSampleThreads) sample_kernel(
       const int mid = (lo + hi) >> 1;
       if (scan[mid] > target) hi = mid; else lo = mid + 1;
     }
+    // Candidates of value -inf (masked logits, the padding) weigh nothing, but the sums of two
+    // neighbouring scan entries associate differently and may differ by a rounding: never draw
+    // one.  Rows without -inf candidates never enter the loop.
+    while (lo > 0 && cv[lo] == -INFINITY) --lo;
     out[row_id] = ci[lo] == 0x7fffffff ? 0 : ci[lo];
   }
 }

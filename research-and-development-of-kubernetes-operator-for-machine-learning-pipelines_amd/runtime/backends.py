@@ -77,6 +77,8 @@ class LLMBackend:
     def __init__(self, engine, metrics=None, tokenizer=None, name: str = "model"):
         self.engine, self.metrics, self.name = engine, metrics, name
         self.tokenizer = tokenizer or ByteTokenizer()
+        if getattr(getattr(engine, "cfg", None), "grammar_states", 0):
+            engine.set_tokenizer(self.tokenizer)  # guided decoding walks the tokens' bytes
         self._pending: list[_Req] = []
         self._active: dict[int, _Req] = {}
         self._lock = threading.Lock()
@@ -184,6 +186,13 @@ class LLMBackend:
         """ValueError (HTTP 400) for what this predictor cannot serve: an adapter it has not loaded."""
         if params.adapter is not None and params.adapter not in getattr(self.engine, "_adapters", {}):
             raise ValueError(f"unknown adapter {params.adapter!r}")
+        if params.guided is not None:
+            # compiled here, in the HTTP handler's thread (cached by spec): the engine thread's
+            # add_request finds it in the cache, the step loop never compiles
+            compile_guided = getattr(self.engine, "compile_guided", None)
+            if compile_guided is None:
+                raise ValueError("this predictor serves no guided requests")
+            compile_guided(params)
 
     def _kv_dtype(self) -> str:
         return str(getattr(getattr(self.engine, "cfg", None), "kv_cache_dtype", "bf16"))
@@ -199,6 +208,10 @@ class LLMBackend:
         ads = self.engine.adapters() if getattr(self.engine, "lora", None) is not None else []
         if ads:  # only when some are configured: the response is unchanged otherwise
             md["adapters"] = [{"name": a["name"], "rank": a["rank"]} for a in ads]
+        if getattr(getattr(self.engine, "cfg", None), "grammar_states", 0):  # (likewise)
+            md["guided_decoding"] = True
+            md["grammar_states"] = int(self.engine.cfg.grammar_states)
+            md["grammar_arena_bytes"] = int(self.engine.stats.get("grammar_arena_bytes", 0))
         return md
 
 

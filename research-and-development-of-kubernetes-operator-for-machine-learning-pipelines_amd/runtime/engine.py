@@ -25,6 +25,10 @@ Step policy:
     drafts: each row feeds its last token and up to k drafts, every token is sampled, the leading
     drafts the sampler reproduced are accepted; it replays the verify graph of its bucket.
     Such an engine steps synchronously.
+  * with ``grammar_states`` > 0 (guided decoding, runtime/guided.py) a request may carry a regex,
+    a list of choices or a JSON schema: its compiled token table lives in a device arena, its
+    automaton state in a device vector indexed by engine row; the sampler masks the row's logits
+    by the state before the draw and advances the state behind it, so the host never reads it.
 """
 from __future__ import annotations
 
@@ -33,6 +37,7 @@ import itertools
 import operator
 import os
 import sys
+import threading
 import time
 from dataclasses import dataclass, field
 from enum import Enum
@@ -189,6 +194,8 @@ class Sequence:
     logprobs: list = field(default_factory=list)  # per output token (logprob, [(id, logprob), ...]) when asked for
     slot: int = -1                              # LoRA adapter slot (-1: base model); kept across preemption
     prefix_seed: bytes = b""                    # seed of the prefix hash chain: the adapter's identity
+    grammar: object = None                      # guided decoding: the compiled guided.Grammar (pinned)
+    g_admitted: bool = False                    # ... and whether the sequence's row holds a reference on its arena range
 
     @property
     def length(self) -> int:
@@ -254,6 +261,12 @@ class EngineConfig:
     spec_ngram_max: int = 3
     spec_ngram_min: int = 1
     spec_max_batch: int = 16
+    # guided decoding (runtime/guided.py): rows of the device arena of compiled grammars (int16
+    # [grammar_states, vocab rounded up to 8]; a grammar takes one row per automaton state) and the
+    # number of compiled grammars the host keeps.  0 = off: nothing is allocated and a guided
+    # request is refused.  Not with tensor or expert parallelism.
+    grammar_states: int = 0
+    grammar_cache: int = 16
 
 
 @dataclass
@@ -394,6 +407,10 @@ class Engine:
         self._slot_refs = np.zeros(max(0, cfg.max_adapters), np.int64)  # live sequences per slot
         self.graphs_lora: dict[int, tuple] = {}
         self._step_lora = False  # the step being launched has at least one adapter row
+        # guided decoding: the grammar arena and the per-row automaton state, allocated before
+        # the KV pool is sized from what is left
+        self.stats = collections.Counter()
+        self._guided_init(cfg, model)
         nb = cfg.num_kv_blocks or self._auto_blocks()
         tp = model.ps.tp
         self.step_sync = StepSync(tp, model.ps.tp_cpu) if tp.size > 1 else None
@@ -463,6 +480,7 @@ class Engine:
         self.r_want = np.full(R, -1, np.int32)
         self.r_sampler = np.zeros(R, bool)
         self.r_slot = np.full(R, -1, np.int32)  # the row's LoRA adapter slot (-1: base model)
+        self.r_gbase = np.full(R, -1, np.int32)  # first arena row of the row's grammar (-1: not guided)
         self.pen_table = None  # int32 [penalty_slots, vocab]: allocated by the first request that needs it
         self.free_pen_slots = list(range(max(0, cfg.penalty_slots) - 1, -1, -1))
         self._last_lp = None   # the last _sample's (logprobs, ids) device tensors, or None
@@ -485,7 +503,6 @@ class Engine:
         self._decode_since_prefill = 0
         self.graphs: dict[int, tuple] = {}
         self.graph_pool = None
-        self.stats = collections.Counter()
         self.stats["kv_pages_released"] = 0
         if self.fp8_kv:
             # (only when it is not the default: the other entries are counters that callers
@@ -710,6 +727,113 @@ class Engine:
         reasons = self._retire_rows(rows, fin, fin_stop)
         return StepBatch(sids, np.asarray(toks, dtype=np.int64), fin_t, reasons, lps)
 
+    # -------------------------------------------------- guided decoding --
+    def _guided_init(self, cfg, model):
+        """The grammar arena (int16 [grammar_states, ldv]) and the per-row automaton state, the
+        host-side cache of compiled grammars and the list of those resident in the arena."""
+        n = cfg.grammar_states
+        self.g_arena = self.g_state = self._tok_bytes = None
+        self._g_cache: collections.OrderedDict = collections.OrderedDict()
+        self._g_lock = threading.Lock()
+        self._g_resident: list = []
+        self._g_tick = 0
+        if not n:
+            return
+        from .guided import MAX_STATES
+
+        if isinstance(n, bool) or not isinstance(n, int) or not 0 < n <= MAX_STATES:
+            raise ValueError(f"grammar_states must be an int in [0, {MAX_STATES}], got {n!r}")
+        if not isinstance(cfg.grammar_cache, int) or cfg.grammar_cache < 1:
+            raise ValueError(f"grammar_cache must be an int >= 1, got {cfg.grammar_cache!r}")
+        if model.ps.tp.size > 1 or model.ps.ep.size > 1:
+            raise ValueError("grammar_states > 0 is not supported with tensor or expert parallelism")
+        self.g_arena = ops.grammar_arena(n, model.cfg.vocab_size, self.device)
+        self.g_state = torch.zeros(cfg.max_num_seqs, dtype=torch.int32, device=self.device)
+        self.stats["grammar_arena_bytes"] = self.g_arena.numel() * 2
+        self.stats["guided_rows"] = 0
+
+    def set_tokenizer(self, tokenizer) -> None:
+        """The tokenizer whose ids this engine's requests use: guided decoding walks the bytes of
+        its tokens (ValueError for a tokenizer it cannot read).  Compiled grammars are dropped."""
+        from .guided import token_bytes
+
+        tb = token_bytes(tokenizer, self.model.cfg.vocab_size) if self.g_arena is not None else None
+        with self._g_lock:
+            self._tok_bytes = tb
+            self._g_cache.clear()
+
+    def compile_guided(self, params: SamplingParams):
+        """The compiled grammar of a guided request, from the cache or compiled here, in the
+        caller's thread; ValueError for what this engine cannot serve."""
+        from . import guided
+
+        if self.g_arena is None:
+            raise ValueError("this engine serves no guided requests (grammar_states = 0)")
+        if self._tok_bytes is None:
+            raise ValueError("guided decoding needs the tokenizer (Engine.set_tokenizer)")
+        if params.ignore_eos:
+            raise ValueError("guided requests end with EOS: ignore_eos cannot be combined with guided")
+        key = guided.spec_key(params.guided)
+        with self._g_lock:
+            g = self._g_cache.get(key)
+            if g is not None:
+                self._g_cache.move_to_end(key)
+                return g
+            tb = self._tok_bytes
+        g = guided.compile(params.guided, tb, self.model.cfg.eos_ids, self.cfg.grammar_states)
+        with self._g_lock:
+            if tb is self._tok_bytes:
+                g = self._g_cache.setdefault(key, g)
+                while len(self._g_cache) > self.cfg.grammar_cache:
+                    self._g_cache.popitem(last=False)
+        return g
+
+    def _grammar_place(self, g) -> bool:
+        """Make ``g`` resident in the arena: first fit over the free ranges; while none is large
+        enough, the least recently used grammar no admitted row refers to gives up its range.
+        False: the arena is held by live requests (the caller waits).  The upload is one copy on
+        the engine's stream, behind every launched step that still reads the range."""
+        self._g_tick += 1
+        g.tick = self._g_tick
+        if g.base >= 0:
+            return True
+        S, A = g.num_states, self.cfg.grammar_states
+        while True:
+            pos = 0
+            for r in sorted(self._g_resident, key=lambda r: r.base):
+                if r.base - pos >= S:
+                    break
+                pos = r.base + r.num_states
+            if pos + S <= A and all(pos + S <= r.base or r.base + r.num_states <= pos for r in self._g_resident):
+                break
+            idle = [r for r in self._g_resident if r.refs == 0]
+            if not idle:
+                return False
+            victim = min(idle, key=lambda r: r.tick)
+            victim.base = -1
+            self._g_resident.remove(victim)
+            self.stats["grammar_evictions"] += 1
+        V = g.next.shape[1]
+        self.g_arena[pos:pos + S, :V].copy_(torch.from_numpy(g.next), non_blocking=False)
+        g.base = pos
+        self._g_resident.append(g)
+        self.stats["grammar_uploads"] += 1
+        return True
+
+    def _admit_guided(self, seq: Sequence) -> bool:
+        """A guided request takes its row: its grammar becomes resident (False: no range, it
+        waits) and the row's state is set on the engine's stream: 0, or after preemption the
+        state reached by walking the output so far through the host copy of the table."""
+        g = seq.grammar
+        if not self._grammar_place(g):
+            return False
+        g.refs += 1
+        seq.g_admitted = True
+        r = seq.row
+        self.g_state[r:r + 1].fill_(g.walk(seq.output))
+        self.r_gbase[r] = g.base
+        return True
+
     # ----------------------------------------------------------- sizing --
     def _auto_blocks(self) -> int:
         mc, m = self.model.cfg, self.model
@@ -750,6 +874,8 @@ class Engine:
             raise ValueError("this engine serves no penalised requests (penalty_slots = 0)")
         if params.adapter is not None and params.adapter not in self._adapters:
             raise ValueError(f"unknown adapter {params.adapter!r} (loaded: {sorted(self._adapters)})")
+        if params.guided is not None:
+            self.compile_guided(params)  # compiles it (or finds it in the cache): ValueError for a bad one
 
     def add_request(self, prompt, params: SamplingParams | None = None, seq_id: int | None = None) -> Sequence:
         params = params or SamplingParams()
@@ -761,6 +887,9 @@ class Engine:
             ad = self._adapters[params.adapter]
             seq.slot, seq.prefix_seed = ad["slot"], ad["seed"]
             self._slot_refs[seq.slot] += 1
+        if params.guided is not None:
+            # pinned: the sequence keeps its compiled grammar whatever the cache drops meanwhile
+            seq.grammar = self.compile_guided(params)
         self.seqs[sid] = seq
         self.waiting.append(seq)
         return seq
@@ -833,8 +962,13 @@ class Engine:
             # on the stream: the next owner's penalty_reset is enqueued behind them
             self.free_pen_slots.append(seq.pen_slot)
             seq.pen_slot = -1
+        if seq.g_admitted:
+            # the grammar stays resident until its range is needed (_grammar_place)
+            seq.grammar.refs -= 1
+            seq.g_admitted = False
         if seq.row >= 0:
             self.r_pen_slot[seq.row], self.r_want[seq.row] = -1, -1
+            self.r_gbase[seq.row] = -1
             self.r_slot[seq.row] = -1
             self.r_nblk[seq.row] = 0
             self.r_nrel[seq.row] = 0
@@ -853,10 +987,13 @@ class Engine:
         self.r_sampler[r] = (not p.greedy) or p.extended
         self.r_want[r] = -1 if p.logprobs is None else p.logprobs
         self.r_pen_slot[r] = -1
+        self.r_gbase[r] = -1
+        if p.penalised and not self.free_pen_slots:
+            return False
+        if seq.grammar is not None and not self._admit_guided(seq):
+            return False  # the arena is held by live requests: it waits, like for a table slot
         if not p.penalised:
             return True
-        if not self.free_pen_slots:
-            return False
         if self.pen_table is None:
             self.pen_table = ops.penalty_table(self.cfg.penalty_slots, self.model.cfg.vocab_size, self.device)
             self.stats["penalty_table_bytes"] = self.pen_table.numel() * 4
@@ -868,12 +1005,17 @@ class Engine:
 
     def _ext_of(self, rows):
         """The sampler-extension arrays of a step's logits rows (None: no row uses them)."""
-        slots, want = self.r_pen_slot[rows], self.r_want[rows]
-        if not ((slots >= 0).any() or (want >= 0).any()):
+        slots, want, gbase = self.r_pen_slot[rows], self.r_want[rows], self.r_gbase[rows]
+        guided = self.g_arena is not None and bool((gbase >= 0).any())
+        if not ((slots >= 0).any() or (want >= 0).any() or guided):
             return None
         self.stats["sampler_ext_rows"] += int(((slots >= 0) | (want >= 0)).sum())
+        if not guided:
+            return SamplerExt(self.pen_table, slots, self.r_rep[rows], self.r_freq[rows], self.r_pres[rows], want,
+                              self.model.cfg.vocab_size)
+        self.stats["guided_rows"] += int((gbase >= 0).sum())
         return SamplerExt(self.pen_table, slots, self.r_rep[rows], self.r_freq[rows], self.r_pres[rows], want,
-                          self.model.cfg.vocab_size)
+                          self.model.cfg.vocab_size, self.g_arena, gbase, rows, self.g_state)
 
     def _register_running(self, s: Sequence, in_flight: int = 0):
         """Row registers of a sequence that joins the running rows; ``in_flight`` = 1: its first

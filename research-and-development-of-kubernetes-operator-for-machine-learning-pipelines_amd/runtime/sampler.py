@@ -11,6 +11,9 @@ every draw, so a draw launched one step ahead of the host still sees the previou
 (``torch.ops.mlop.apply_penalties`` / ``penalty_update`` / ``penalty_reset``).  Log-probabilities
 are the log-softmax of the logits as the model emitted them (before penalties, temperature and
 truncation), by ``torch.ops.mlop.token_logprobs`` straight from the bf16 rows.
+
+Guided decoding (runtime/guided.py) is the same pattern with another table: a per-row automaton
+state on the device, ``grammar_mask`` before the draw and ``grammar_advance`` behind it.
 """
 from __future__ import annotations
 
@@ -42,6 +45,9 @@ class SamplingParams:
     frequency_penalty: float = 0.0    # subtracted per occurrence in the output so far
     logprobs: int | None = None       # None: off; N: the token's logprob + the top N alternatives
     adapter: str | None = None        # name of a loaded LoRA adapter (Engine.load_adapter); None: the base model
+    # guided decoding (runtime/guided.py): exactly one of {"choice": [str, ...]}, {"regex": str},
+    # {"json_schema": dict | str}; the output then fully matches it (engines with grammar_states > 0)
+    guided: dict | None = None
 
     @property
     def greedy(self) -> bool:
@@ -53,8 +59,9 @@ class SamplingParams:
 
     @property
     def extended(self) -> bool:
-        """Needs the sampler's extended path (count-table slot and / or log-probabilities)."""
-        return self.logprobs is not None or self.penalised
+        """Needs the sampler's extended path (count-table slot, log-probabilities and / or a
+        grammar state)."""
+        return self.logprobs is not None or self.penalised or self.guided is not None
 
     def validate(self) -> "SamplingParams":
         """Raise ValueError for parameters no sampler can honour (a bad request fails alone)."""
@@ -91,6 +98,10 @@ class SamplingParams:
             raise ValueError(f"logprobs must be None or an int in [0, {MAX_LOGPROBS}], got {n}")
         if self.adapter is not None and (not isinstance(self.adapter, str) or not self.adapter):
             raise ValueError(f"adapter must be None or a non-empty string, got {self.adapter!r}")
+        if self.guided is not None:
+            from .guided import check_spec
+
+            check_spec(self.guided)  # the shape only: Engine.check_request compiles it
         return self
 
 
@@ -217,12 +228,18 @@ def logprobs_reference(out_lp: torch.Tensor, out_id: torch.Tensor, logits: torch
 class SamplerExt:
     """What the extended path needs besides the rows' SamplingParams: the count table and, per
     row of the logits, the table slot (-1: no penalty), the three penalties and the number of
-    top log-probabilities wanted (-1: none)."""
+    top log-probabilities wanted (-1: none).  Guided rows: the grammar arena, per row of the
+    logits the first arena row of its grammar (``gbase``, -1: not guided) and its engine row
+    (``rows``), and the per-engine-row automaton state on the device (``gstate``)."""
 
-    __slots__ = ("table", "slots", "rep", "freq", "pres", "want", "vocab")
+    __slots__ = ("table", "slots", "rep", "freq", "pres", "want", "vocab", "arena", "gbase", "rows", "gstate")
 
-    def __init__(self, table, slots, rep, freq, pres, want, vocab=None):
+    def __init__(self, table, slots, rep, freq, pres, want, vocab=None, arena=None, gbase=None, rows=None,
+                 gstate=None):
         self.table, self.vocab = table, vocab
+        self.arena, self.gstate = arena, gstate
+        self.gbase = None if gbase is None else np.ascontiguousarray(gbase, dtype=np.int32)
+        self.rows = None if rows is None else np.ascontiguousarray(rows, dtype=np.int32)
         self.slots = np.ascontiguousarray(slots, dtype=np.int32)
         self.rep = np.ascontiguousarray(rep, dtype=np.float32)
         self.freq = np.ascontiguousarray(freq, dtype=np.float32)
@@ -239,9 +256,9 @@ class Sampler:
     def sample_ext(self, logits: torch.Tensor, params, ext: SamplerExt, gen_index=None):
         """Draw with penalties and / or log-probabilities: (tokens int64 [n], lp f32 [n, 1 + N] or
         None, ids int32 [n, 1 + N] or None), N = the largest ``want`` of the batch.  fp32 copy ->
-        ``apply_penalties`` -> the plain draw on the penalised rows -> ``penalty_update`` ->
-        ``token_logprobs`` on the ORIGINAL logits.  Rows without a slot draw from untouched rows, so
-        they get the tokens the plain path gives them."""
+        ``apply_penalties`` -> ``grammar_mask`` -> the plain draw on those rows -> ``grammar_advance``
+        -> ``penalty_update`` -> ``token_logprobs`` on the ORIGINAL logits.  Rows without a slot or a
+        grammar draw from untouched rows, so they get the tokens the plain path gives them."""
         n = logits.shape[0]
         dev = logits.device
 
@@ -249,14 +266,22 @@ class Sampler:
             return torch.from_numpy(a).to(dev, non_blocking=True)
 
         penalised = bool((ext.slots >= 0).any())
-        if penalised:
+        guided = ext.gbase is not None and bool((ext.gbase >= 0).any())
+        if penalised or guided:
             work = logits.float()
             if work.data_ptr() == logits.data_ptr():
                 work = work.clone()  # never the caller's tensor
-            slots_d = put(ext.slots)
-            ops.apply_penalties(work, ext.table, slots_d, put(ext.rep), put(ext.freq), put(ext.pres))
+            if penalised:
+                slots_d = put(ext.slots)
+                ops.apply_penalties(work, ext.table, slots_d, put(ext.rep), put(ext.freq), put(ext.pres))
+            if guided:
+                gbase_d, rows_d = put(ext.gbase), put(ext.rows)
+                ops.grammar_mask(work, ext.arena, gbase_d, rows_d, ext.gstate)
             toks = self(work, params, gen_index)
-            ops.penalty_update(ext.table, slots_d, toks, ext.vocab)
+            if guided:
+                ops.grammar_advance(ext.arena, gbase_d, rows_d, ext.gstate, toks, ext.vocab)
+            if penalised:
+                ops.penalty_update(ext.table, slots_d, toks, ext.vocab)
         else:
             toks = self(logits, params, gen_index)
         nmax = int(ext.want.max()) if n else -1

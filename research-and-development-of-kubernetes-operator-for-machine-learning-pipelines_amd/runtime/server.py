@@ -130,7 +130,31 @@ def _params(p: dict) -> SamplingParams:
     ad = p.get("adapter")
     if ad is not None and not isinstance(ad, str):
         raise ValueError(f"adapter must be a string, got {ad!r}")
-    return SamplingParams(adapter=ad, max_tokens=int(p.get("max_tokens", 64)), temperature=float(p.get("temperature", 0.0)),
+    # guided decoding: at most one of guided_choice / guided_regex / guided_json
+    given = [k for k in ("guided_choice", "guided_regex", "guided_json") if p.get(k) is not None]
+    if len(given) > 1:
+        raise ValueError(f"at most one of guided_choice / guided_regex / guided_json, got {given}")
+    guided = None
+    if given:
+        v = p[given[0]]
+        if given[0] == "guided_choice":
+            if not isinstance(v, list) or not v or any(not isinstance(c, str) for c in v):
+                raise ValueError("guided_choice must be a non-empty list of strings")
+            guided = {"choice": v}
+        elif given[0] == "guided_regex":
+            if not isinstance(v, str):
+                raise ValueError(f"guided_regex must be a string, got {type(v).__name__}")
+            guided = {"regex": v}
+        else:
+            if isinstance(v, str):
+                try:
+                    v = json.loads(v)
+                except ValueError as e:
+                    raise ValueError(f"guided_json is not valid JSON: {e}") from None
+            if not isinstance(v, dict):
+                raise ValueError("guided_json must be a JSON schema object (or its JSON text)")
+            guided = {"json_schema": v}
+    return SamplingParams(adapter=ad, guided=guided,max_tokens=int(p.get("max_tokens", 64)), temperature=float(p.get("temperature", 0.0)),
                           top_k=int(p.get("top_k", 0)), top_p=float(p.get("top_p", 1.0)),
                           ignore_eos=bool(p.get("ignore_eos", False)),
                           stop_token_ids=list(p.get("stop_token_ids", [])),
