@@ -43,6 +43,9 @@ class ModelConfig:
     # sliding-window attention (Mistral): the query at position i attends the keys
     # i - W < j <= i on every layer; 0 = full causal attention
     sliding_window: int = 0
+    # per-head QK-norm (Qwen3): an RMSNorm with a learned [head_dim] weight on every q head and
+    # every k head between the QKV projection and RoPE (layer weights "q_norm" / "k_norm")
+    qk_norm: bool = False
 
     @property
     def eos_ids(self) -> tuple:
@@ -65,7 +68,7 @@ class ModelConfig:
         attn = H * (self.q_size + 2 * self.kv_size) + self.q_size * H
         mlp = 3 * H * I * (self.num_experts if self.is_moe else 1)
         router = H * self.num_experts if self.is_moe else 0
-        norms = 2 * H
+        norms = 2 * H + (2 * self.head_dim if self.qk_norm else 0)
         emb = V * H * (1 if self.tie_embeddings else 2)
         return L * (attn + mlp + router + norms) + emb + H
 
@@ -136,8 +139,25 @@ TINY_MIXTRAL = ModelConfig(
 TINY_LLAMA_8H = replace(TINY_LLAMA, name="tiny-llama-8h", num_heads=8)
 TINY_MIXTRAL_8E = replace(TINY_MIXTRAL, name="tiny-mixtral-8e", num_experts=8)
 
+# Qwen3 (dense): TINY_LLAMA with the per-head QK-norm and Qwen3's eps / theta
+TINY_QWEN3 = replace(TINY_LLAMA, name="tiny-qwen3", qk_norm=True, rms_eps=1e-6, rope_theta=1e6)
+
+# Qwen3-8B / -32B: public HF config.json of Qwen/Qwen3-8B and Qwen/Qwen3-32B (Llama layout,
+# head_dim 128, GQA 4 / 8, per-head QK-norm)
+QWEN3_8B = ModelConfig(
+    name="qwen3-8b", vocab_size=151936, hidden_size=4096, intermediate_size=12288, num_layers=36,
+    num_heads=32, num_kv_heads=8, rope_theta=1e6, rms_eps=1e-6, max_position=40960, eos_token_id=151645,
+    qk_norm=True)
+QWEN3_32B = replace(QWEN3_8B, name="qwen3-32b", hidden_size=5120, intermediate_size=25600, num_layers=64,
+                    num_heads=64)
+
 PRESETS = {c.name: c for c in (LLAMA3_8B, LLAMA3_70B, LLAMA31_8B, LLAMA31_70B, MIXTRAL_8X7B, MISTRAL_7B, TINY_LLAMA,
-                                TINY_MIXTRAL, TINY_LLAMA_8H, TINY_MIXTRAL_8E)}
+                                TINY_MIXTRAL, TINY_LLAMA_8H, TINY_MIXTRAL_8E, TINY_QWEN3)}
+# Real-size shapes that are served but are NOT in PRESETS: the GEMM planner's pinned route table
+# (tests/fixtures/gemm_routes_gfx950.txt) is derived from every non-tiny PRESETS entry, so a new
+# entry there would change that yardstick.  get_config, ALIASES and loader.known_preset look here
+# too; the routes of these shapes are pinned in a fixture of their own.
+CHECKPOINT_SHAPES = {c.name: c for c in (QWEN3_8B, QWEN3_32B)}
 # accepted aliases (MLflow tags / CR annotations use HF-ish names)
 ALIASES = {
     "meta-llama/Meta-Llama-3-8B": "llama3-8b", "llama-3-8b": "llama3-8b", "Llama-3-8B": "llama3-8b",
@@ -146,12 +166,13 @@ ALIASES = {
     "meta-llama/Llama-3.1-70B": "llama3.1-70b", "meta-llama/Meta-Llama-3.1-70B": "llama3.1-70b",
     "mistralai/Mixtral-8x7B-v0.1": "mixtral-8x7b", "Mixtral-8x7B": "mixtral-8x7b",
     "mistralai/Mistral-7B-v0.1": "mistral-7b", "Mistral-7B": "mistral-7b",
+    "Qwen/Qwen3-8B": "qwen3-8b", "Qwen3-8B": "qwen3-8b", "Qwen/Qwen3-32B": "qwen3-32b", "Qwen3-32B": "qwen3-32b",
 }
 
 
 def get_config(name: str, **overrides) -> ModelConfig:
     key = ALIASES.get(name, name)
-    if key not in PRESETS:
-        raise KeyError(f"unknown model '{name}' (known: {sorted(PRESETS)})")
-    cfg = PRESETS[key]
+    cfg = PRESETS.get(key) or CHECKPOINT_SHAPES.get(key)
+    if cfg is None:
+        raise KeyError(f"unknown model '{name}' (known: {sorted([*PRESETS, *CHECKPOINT_SHAPES])})")
     return replace(cfg, **overrides) if overrides else cfg

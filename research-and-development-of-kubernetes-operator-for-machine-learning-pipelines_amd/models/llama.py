@@ -54,6 +54,9 @@ class LlamaModel:
                 "qkv": w((self.n_q + 2 * self.n_kv) * D, H),
                 "o": w(H, self.n_q * D),
             }
+            if cfg.qk_norm:  # per head, so replicated over TP ranks
+                layer["q_norm"] = init_norm(D, self.device, dtype)
+                layer["k_norm"] = init_norm(D, self.device, dtype)
             layer.update(self._init_mlp(w))
             self.layers.append(layer)
         self.final_norm = init_norm(H, self.device, dtype)
@@ -86,6 +89,9 @@ class LlamaModel:
             cp(L["o"], F["o"][:, qs])
             cp(L["in_norm"], F["in_norm"])
             cp(L["post_norm"], F["post_norm"])
+            if cfg.qk_norm:
+                cp(L["q_norm"], F["q_norm"])
+                cp(L["k_norm"], F["k_norm"])
             self._shard_mlp(L, F)
         cp(self.final_norm, full.final_norm)
         if self.lm_head is not self.embed:
@@ -98,7 +104,8 @@ class LlamaModel:
         """Fold each RMSNorm weight into the projection that consumes it (in_norm -> qkv,
         post_norm -> gate_up: W[:, k] *= g[k]) and set the norm weights to ones, so the large-M
         forward can apply the normalisation as a per-row factor after the GEMM (norm chain).
-        The same function up to the bf16 rounding of g * W."""
+        The same function up to the bf16 rounding of g * W.  A QK-norm model's q_norm / k_norm
+        stay as they are: they act after the projection, so there is nothing to fold them into."""
         # the folded weights stay available (a few KB per layer): a LoRA adapter loaded later
         # needs the same fold on the A matrices that read the normalised input (models/lora.py)
         prev = getattr(self, "folded_norms", None)
@@ -175,8 +182,10 @@ class LlamaModel:
         # fp8 KV cache: the QKV epilogues that write the cache (fused RoPE, and the norm chain's
         # row-scaled forms of it) are bf16-only, so the layer runs unfused - norm, plain QKV GEMM,
         # kv_fp8.hip's RoPE + quantising writer - and every chain form is off
+        # QK-norm (Qwen3): the same unfused layer at every M and TP size, the stand-alone writer
+        # being rope_cache_qkn.hip's (the QKV epilogues know nothing of the per-head norm)
         fp8 = getattr(kv, "fp8", False)
-        chain = not fp8 and (tp.size == 1 or M <= dmax) and self._chain_ok(M)
+        chain = not fp8 and not cfg.qk_norm and (tp.size == 1 or M <= dmax) and self._chain_ok(M)
         ss = None  # norm chain: x is None and ss holds the residual's row partials
         if chain and M <= dmax:
             # decode form: the QKV GEMV takes the embedding rows' factors itself (ss unused)
@@ -184,7 +193,10 @@ class LlamaModel:
         else:
             x = ops.rmsnorm(h, self.layers[0]["in_norm"], eps)
         for i, L in enumerate(self.layers):
-            if fp8:
+            if cfg.qk_norm:
+                q = ops.rope_cache(ops.gemm(x, L["qkv"]), meta.positions, self.cos_sin, meta.slots, kv.k[i], kv.v[i],
+                                   self.n_q, q_norm=L["q_norm"], k_norm=L["k_norm"], eps=eps, **kv.scales(i))
+            elif fp8:
                 q = ops.rope_cache(ops.gemm(x, L["qkv"]), meta.positions, self.cos_sin, meta.slots, kv.k[i], kv.v[i],
                                    self.n_q, **kv.scales(i))
             elif ss is None:
@@ -228,8 +240,9 @@ class LlamaModel:
         x = ops.rmsnorm(residual, self.layers[0]["in_norm"], eps)
         for i, (L, S) in enumerate(zip(self.layers, lora.layers)):
             qkv = proj(x, L, S, "qkv")
+            qkn = {"q_norm": L["q_norm"], "k_norm": L["k_norm"], "eps": eps} if self.cfg.qk_norm else {}
             q = ops.rope_cache(qkv, meta.positions, self.cos_sin, meta.slots, kv.k[i], kv.v[i], self.n_q,
-                               **kv.scales(i))
+                               **qkn, **kv.scales(i))
             a = ops.paged_attention(q, kv.k[i], kv.v[i], meta, **kv.scales(i))
             o = proj(a.view(a.shape[0], -1), L, S, "o")
             x = ops.add_rmsnorm(o, residual, L["post_norm"], eps)

@@ -3,7 +3,7 @@
 The operator hands a predictor its MLflow artifact URI (``s3://mlflow/<rel>``, reference
 ``mlflow_operator.py:125-127``).  When that artifact is reachable as a local directory
 (``file://`` URI, a plain path, or ``s3://mlflow/<rel>`` under ``MLOP_ARTIFACT_ROOT``)
-holding a Llama / Mistral / Mixtral checkpoint in the HF layout, the runtime serves those weights;
+holding a Llama / Mistral / Mixtral / Qwen3 (dense) checkpoint in the HF layout, the runtime serves those weights;
 otherwise it random-initialises the architecture named by the CR / MLflow tags (the
 benchmark configuration: no checkpoints are downloadable here).
 
@@ -11,6 +11,7 @@ Layout mapping (HF name -> ours; TP sharding then reuses ``load_shard_from``):
   model.embed_tokens / lm_head / model.norm       -> embed / lm_head / final_norm
   self_attn.{q,k,v}_proj                         -> qkv  ([q; k; v] rows, rotate-half RoPE as HF)
   self_attn.o_proj                               -> o
+  self_attn.{q,k}_norm (Qwen3)                   -> q_norm / k_norm  (per head, replicated over TP)
   input_layernorm / post_attention_layernorm     -> in_norm / post_norm
   mlp.{gate,up}_proj                             -> gate_up (rows interleaved in groups of 16:
                                                     the GEMM's SiLU-mul epilogue layout)
@@ -30,9 +31,13 @@ from pathlib import Path
 
 import torch
 
-from .config import ModelConfig, PRESETS
+from .config import CHECKPOINT_SHAPES, ModelConfig, PRESETS
 
-_ARCH_NAMES = {"LlamaForCausalLM": "llama", "MixtralForCausalLM": "mixtral", "MistralForCausalLM": "llama"}
+# Qwen3 (dense) is the Llama layer with a per-head QK-norm before RoPE (ModelConfig.qk_norm)
+_ARCH_NAMES = {"LlamaForCausalLM": "llama", "MixtralForCausalLM": "mixtral", "MistralForCausalLM": "llama",
+               "Qwen3ForCausalLM": "llama"}
+# GQA groups the attention bindings take (bindings.cpp: decode "GQA group must divide 16"; flash prefill 1, 2, 4, 8)
+_GQA_GROUPS = (1, 2, 4, 8, 16)
 
 
 def _is_checkpoint(d: Path) -> bool:
@@ -71,8 +76,11 @@ def resolve_model_dir(uri: str | None, marker=_is_checkpoint) -> Path | None:
 
 
 def config_from_hf(d: dict, name: str | None = None) -> ModelConfig:
-    """ModelConfig from an HF ``config.json`` dict (Llama / Mistral / Mixtral families)."""
+    """ModelConfig from an HF ``config.json`` dict (Llama / Mistral / Mixtral / dense Qwen3 families)."""
     arch = (d.get("architectures") or ["LlamaForCausalLM"])[0]
+    if arch == "Qwen3MoeForCausalLM":
+        raise ValueError("Qwen3-MoE checkpoints are not supported: their router (norm_topk_prob, 128 experts) "
+                         "differs from Mixtral's; only the dense Qwen3ForCausalLM loads")
     if arch not in _ARCH_NAMES:
         raise ValueError(f"unsupported checkpoint architecture {arch!r} (supported: {sorted(_ARCH_NAMES)})")
     if d.get("hidden_act", "silu") != "silu":
@@ -108,18 +116,25 @@ def config_from_hf(d: dict, name: str | None = None) -> ModelConfig:
     for flag in ("attention_bias", "mlp_bias"):
         if d.get(flag):
             raise ValueError(f"{flag}=true is not supported (bias tensors are not loaded)")
+    nkv = d.get("num_key_value_heads") or nh
+    qk_norm = arch == "Qwen3ForCausalLM"
+    if qk_norm and (nh % nkv or nh // nkv not in _GQA_GROUPS):
+        # (Qwen3-14B: 40 query heads over 8 KV heads) fail here, not in a device-path check
+        raise ValueError(f"GQA group {nh}/{nkv} = {nh / nkv:g} is not supported: the attention kernels take "
+                         f"groups of {', '.join(map(str, _GQA_GROUPS))}")
     eos = d.get("eos_token_id", 2)
     eos_all = tuple(int(e) for e in eos) if isinstance(eos, list) else ((int(eos),) if eos is not None else (2,))
     eos = eos_all[0]
     return ModelConfig(
         name=name or d.get("_name_or_path") or arch, vocab_size=d["vocab_size"], hidden_size=H,
         intermediate_size=d["intermediate_size"], num_layers=d["num_hidden_layers"], num_heads=nh,
-        num_kv_heads=d.get("num_key_value_heads") or nh, head_dim=d.get("head_dim") or H // nh,
+        num_kv_heads=nkv, head_dim=d.get("head_dim") or H // nh,
         rope_theta=float(theta), rms_eps=float(d.get("rms_norm_eps", 1e-5)),
         max_position=max_pos,
         tie_embeddings=bool(d.get("tie_word_embeddings", False)),
         num_experts=int(d.get("num_local_experts", 0) or 0), top_k=int(d.get("num_experts_per_tok", 2)),
-        rope_scaling=scaling, eos_token_id=int(eos), extra_eos_ids=eos_all[1:], sliding_window=window)
+        rope_scaling=scaling, eos_token_id=int(eos), extra_eos_ids=eos_all[1:], sliding_window=window,
+        qk_norm=qk_norm)
 
 
 class _Tensors:
@@ -174,6 +189,9 @@ class HFWeights:
                  "o": lambda: t.get(p + "self_attn.o_proj.weight"),
                  "in_norm": lambda: t.get(p + "input_layernorm.weight"),
                  "post_norm": lambda: t.get(p + "post_attention_layernorm.weight")}
+            if cfg.qk_norm:  # (a Llama checkpoint that carries such tensors is loaded as before)
+                L["q_norm"] = lambda: t.get(p + "self_attn.q_norm.weight")
+                L["k_norm"] = lambda: t.get(p + "self_attn.k_norm.weight")
             if not cfg.is_moe:
                 L["gate_up"] = lambda: interleave_gate_up(t.get(p + "mlp.gate_proj.weight"),
                                                           t.get(p + "mlp.up_proj.weight"))
@@ -222,7 +240,7 @@ def load_pretrained(path: str | os.PathLike, device="cuda", dtype=torch.bfloat16
 
 def known_preset(cfg: ModelConfig) -> str | None:
     """Name of the preset with the same shapes (placement / reporting), if any."""
-    for n, p in PRESETS.items():
+    for n, p in (*PRESETS.items(), *CHECKPOINT_SHAPES.items()):
         if replace(p, name=cfg.name, eos_token_id=cfg.eos_token_id, rope_scaling=cfg.rope_scaling,
                    max_position=cfg.max_position) == cfg:
             return n

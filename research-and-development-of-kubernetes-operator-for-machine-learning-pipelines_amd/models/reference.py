@@ -58,6 +58,9 @@ def dense_logits(model, tokens, kv_cache_dtype: str | None = None) -> torch.Tens
         q = qkv[:, : model.n_q * D].view(T, model.n_q, D)
         k = qkv[:, model.n_q * D:(model.n_q + model.n_kv) * D].view(T, model.n_kv, D)
         v = qkv[:, (model.n_q + model.n_kv) * D:].view(T, model.n_kv, D)
+        if cfg.qk_norm:  # per-head RMSNorm of q and k before the rotation (Qwen3), fp32 throughout
+            q = ref.head_rmsnorm(q, L["q_norm"], cfg.rms_eps)
+            k = ref.head_rmsnorm(k, L["k_norm"], cfg.rms_eps)
         q = ref.rotate(q, cs[:, None, :half], cs[:, None, half:])
         k = ref.rotate(k, cs[:, None, :half], cs[:, None, half:])
         if kv_cache_dtype == "fp8":

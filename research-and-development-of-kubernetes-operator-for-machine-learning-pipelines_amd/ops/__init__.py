@@ -120,21 +120,33 @@ def _fp8_scales(k_cache, k_scale, v_scale) -> bool:
 
 def rope_cache(qkv, positions, cos_sin, slots, k_cache, v_cache, n_q_heads: int,
                q_out: torch.Tensor | None = None, k_scale: torch.Tensor | None = None,
-               v_scale: torch.Tensor | None = None):
+               v_scale: torch.Tensor | None = None, q_norm: torch.Tensor | None = None,
+               k_norm: torch.Tensor | None = None, eps: float = 0.0):
     """RoPE + paged-cache write.  The cache's dtype picks the writer: bf16 pages, or e4m3fn pages
-    with their ``k_scale`` / ``v_scale`` bytes [NB, Hkv, 16] (kv_fp8.hip; ``ref.fp8_quantize_rows``)."""
+    with their ``k_scale`` / ``v_scale`` bytes [NB, Hkv, 16] (kv_fp8.hip; ``ref.fp8_quantize_rows``).
+    ``q_norm`` / ``k_norm`` (bf16 [128], both or neither) with ``eps``: the per-head RMSNorm of
+    every q and k head before the rotation (Qwen3), rope_cache_qkn.hip's writers; without them the
+    launches are the plain writers'."""
+    if (q_norm is None) != (k_norm is None):
+        raise ValueError("QK-norm needs both q_norm and k_norm")
     T = qkv.shape[0]
     D = k_cache.shape[3]
     fp8 = _fp8_scales(k_cache, k_scale, v_scale)
     if not qkv.is_cuda:
-        q = ref.rope_cache(qkv, positions, cos_sin, slots, k_cache, v_cache, n_q_heads, k_scale, v_scale)
+        q = ref.rope_cache(qkv, positions, cos_sin, slots, k_cache, v_cache, n_q_heads, k_scale, v_scale,
+                           q_norm=q_norm, k_norm=k_norm, eps=eps)
         if q_out is not None:
             q_out.copy_(q)
             return q_out
         return q
     _need_gpu()
     q_out = torch.empty(T, n_q_heads, D, dtype=qkv.dtype, device=qkv.device) if q_out is None else q_out
-    if fp8:
+    if q_norm is not None and fp8:
+        torch.ops.mlop.rope_cache_qkn_fp8(q_out, k_cache, v_cache, k_scale, v_scale, qkv, positions, cos_sin, slots,
+                                          q_norm, k_norm, eps)
+    elif q_norm is not None:
+        torch.ops.mlop.rope_cache_qkn(q_out, k_cache, v_cache, qkv, positions, cos_sin, slots, q_norm, k_norm, eps)
+    elif fp8:
         torch.ops.mlop.rope_cache_fp8(q_out, k_cache, v_cache, k_scale, v_scale, qkv, positions, cos_sin, slots)
     else:
         torch.ops.mlop.rope_cache(q_out, k_cache, v_cache, qkv, positions, cos_sin, slots)

@@ -311,6 +311,61 @@ void rope_cache_fp8(Tensor q_out, Tensor k_cache, Tensor v_cache, Tensor k_scale
                               (int)qkv.stride(0), 16, cur_stream());
 }
 
+// ---- per-head QK-norm writers (rope_cache_qkn.hip): rope_cache / rope_cache_fp8 with an RMSNorm
+// of every q and k head before the rotation; head_dim 128 only
+struct QknArgs {
+  int T, Hq, Hkv;
+};
+static QknArgs check_qkn(const Tensor& q_out, const Tensor& k_cache, const Tensor& v_cache, const Tensor& qkv,
+                         const Tensor& pos, const Tensor& cos_sin, const Tensor& slots, const Tensor& q_w,
+                         const Tensor& k_w, double eps) {
+  check_bf16(q_out, "q_out");
+  check_i32(pos, "pos"); check_i32(slots, "slots");
+  TORCH_CHECK(qkv.is_cuda() && qkv.scalar_type() == at::kBFloat16 && qkv.stride(-1) == 1 && qkv.dim() == 2,
+              "qkv must be 2-d bf16 with unit inner stride");
+  TORCH_CHECK(cos_sin.is_cuda() && cos_sin.scalar_type() == at::kFloat && cos_sin.is_contiguous(), "cos_sin f32");
+  TORCH_CHECK(q_out.dim() == 3 && q_out.size(2) == 128, "q_out must be [T, Hq, 128] (QK-norm: head_dim 128 only)");
+  TORCH_CHECK(k_cache.dim() == 4 && k_cache.size(3) == 128 && v_cache.sizes() == k_cache.sizes(),
+              "cache layouts: k and v [NB, Hkv, BS, 128] (token-major)");
+  const int T = (int)q_out.size(0), Hq = (int)q_out.size(1), Hkv = (int)k_cache.size(1);
+  TORCH_CHECK(qkv.size(0) == T && qkv.size(-1) >= (Hq + 2 * Hkv) * 128 && qkv.stride(0) % 8 == 0 &&
+                  (reinterpret_cast<uintptr_t>(qkv.data_ptr()) & 15) == 0,
+              "qkv shape / alignment");
+  TORCH_CHECK(pos.numel() == T && slots.numel() == T, "pos/slots length");
+  TORCH_CHECK(cos_sin.dim() == 2 && cos_sin.size(1) == 128, "cos_sin must be [max_pos, 128]");
+  for (const Tensor* w : {&q_w, &k_w}) {
+    check_bf16(*w, "q_norm / k_norm");
+    TORCH_CHECK(w->dim() == 1 && w->size(0) == 128 && w->is_contiguous() &&
+                    (reinterpret_cast<uintptr_t>(w->data_ptr()) & 15) == 0,
+                "q_norm / k_norm must be contiguous 16-B aligned bf16 [128]");
+  }
+  TORCH_CHECK(eps >= 0, "eps must be >= 0");
+  return {T, Hq, Hkv};
+}
+
+void rope_cache_qkn(Tensor q_out, Tensor k_cache, Tensor v_cache, Tensor qkv, Tensor pos, Tensor cos_sin,
+                    Tensor slots, Tensor q_w, Tensor k_w, double eps) {
+  check_bf16(k_cache, "k_cache"); check_bf16(v_cache, "v_cache");
+  const QknArgs a = check_qkn(q_out, k_cache, v_cache, qkv, pos, cos_sin, slots, q_w, k_w, eps);
+  c10::DeviceGuard g(qkv.device());
+  mlop::launch_rope_cache_qkn(q_out.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), qkv.data_ptr(),
+                              pos.data_ptr<int>(), cos_sin.data_ptr<float>(), slots.data_ptr<int>(), a.T, a.Hq,
+                              a.Hkv, (int)qkv.stride(0), (int)k_cache.size(2), (const uint16_t*)q_w.data_ptr(),
+                              (const uint16_t*)k_w.data_ptr(), (float)eps, cur_stream());
+}
+
+void rope_cache_qkn_fp8(Tensor q_out, Tensor k_cache, Tensor v_cache, Tensor k_scale, Tensor v_scale, Tensor qkv,
+                        Tensor pos, Tensor cos_sin, Tensor slots, Tensor q_w, Tensor k_w, double eps) {
+  check_fp8_cache(k_cache, k_scale, "k_cache"); check_fp8_cache(v_cache, v_scale, "v_cache");
+  const QknArgs a = check_qkn(q_out, k_cache, v_cache, qkv, pos, cos_sin, slots, q_w, k_w, eps);
+  c10::DeviceGuard g(qkv.device());
+  mlop::launch_rope_cache_qkn_fp8(q_out.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), k_scale.data_ptr(),
+                                  v_scale.data_ptr(), qkv.data_ptr(), pos.data_ptr<int>(),
+                                  cos_sin.data_ptr<float>(), slots.data_ptr<int>(), a.T, a.Hq, a.Hkv,
+                                  (int)qkv.stride(0), 16, (const uint16_t*)q_w.data_ptr(),
+                                  (const uint16_t*)k_w.data_ptr(), (float)eps, cur_stream());
+}
+
 void paged_attention_fp8(Tensor out, Tensor part_o, Tensor part_ml, Tensor part_sem, Tensor q, Tensor k_cache,
                          Tensor v_cache, Tensor k_scale, Tensor v_scale, Tensor block_tables, Tensor tile_seq,
                          Tensor tile_q0, Tensor q_start, Tensor q_len, Tensor ctx_len, double scale,
@@ -1220,6 +1275,11 @@ TORCH_LIBRARY(mlop, m) {
         "int nparts, int window=0) -> ()");
   m.def("rope_cache_fp8(Tensor(a!) q_out, Tensor(b!) k_cache, Tensor(c!) v_cache, Tensor(d!) k_scale, "
         "Tensor(e!) v_scale, Tensor qkv, Tensor pos, Tensor cos_sin, Tensor slots) -> ()");
+  m.def("rope_cache_qkn(Tensor(a!) q_out, Tensor(b!) k_cache, Tensor(c!) v_cache, Tensor qkv, Tensor pos, "
+        "Tensor cos_sin, Tensor slots, Tensor q_w, Tensor k_w, float eps) -> ()");
+  m.def("rope_cache_qkn_fp8(Tensor(a!) q_out, Tensor(b!) k_cache, Tensor(c!) v_cache, Tensor(d!) k_scale, "
+        "Tensor(e!) v_scale, Tensor qkv, Tensor pos, Tensor cos_sin, Tensor slots, Tensor q_w, Tensor k_w, "
+        "float eps) -> ()");
   m.def("paged_attention_fp8(Tensor(a!) out, Tensor(b!) part_o, Tensor(c!) part_ml, Tensor(d!) part_sem, Tensor q, "
         "Tensor k_cache, Tensor v_cache, Tensor k_scale, Tensor v_scale, Tensor block_tables, Tensor tile_seq, "
         "Tensor tile_q0, Tensor q_start, Tensor q_len, Tensor ctx_len, float scale, int part_tokens, "
@@ -1236,6 +1296,8 @@ TORCH_LIBRARY_IMPL(mlop, CUDA, m) {
   m.impl("lora_expand_add", &lora_expand_add);
   m.impl("paged_attention", &paged_attention);
   m.impl("rope_cache_fp8", &rope_cache_fp8);
+  m.impl("rope_cache_qkn", &rope_cache_qkn);
+  m.impl("rope_cache_qkn_fp8", &rope_cache_qkn_fp8);
   m.impl("paged_attention_fp8", &paged_attention_fp8);
   m.impl("flash_prefill", &flash_prefill);
   m.impl("gemm", &gemm);

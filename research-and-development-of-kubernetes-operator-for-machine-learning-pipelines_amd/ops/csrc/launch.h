@@ -38,6 +38,15 @@ void launch_paged_attention(void* out, float* part_o, float* part_ml, const void
 void launch_rope_cache_fp8(void* q_out, void* k_cache, void* v_cache, void* k_scale, void* v_scale,
                            const void* qkv, const int* pos, const float* cos_sin, const int* slots, int T,
                            int Hq, int Hkv, int qkv_stride, int BS, hipStream_t st);
+// rope_cache_qkn.hip: the two stand-alone writers with a per-head RMSNorm (weights q_w / k_w, bf16
+// [128]) on every q and k head before the rotation (Qwen3); head_dim 128, layouts as above
+void launch_rope_cache_qkn(void* q_out, void* k_cache, void* v_cache, const void* qkv, const int* pos,
+                           const float* cos_sin, const int* slots, int T, int Hq, int Hkv, int qkv_stride,
+                           int BS, const uint16_t* q_w, const uint16_t* k_w, float eps, hipStream_t st);
+void launch_rope_cache_qkn_fp8(void* q_out, void* k_cache, void* v_cache, void* k_scale, void* v_scale,
+                               const void* qkv, const int* pos, const float* cos_sin, const int* slots, int T,
+                               int Hq, int Hkv, int qkv_stride, int BS, const uint16_t* q_w,
+                               const uint16_t* k_w, float eps, hipStream_t st);
 void launch_paged_attention_fp8(void* out, float* part_o, float* part_ml, const void* q, const void* kc,
                                 const void* vc, const void* ks, const void* vs, const int* bt,
                                 int bt_stride, const int* tile_seq, const int* tile_q0, const int* q_start,

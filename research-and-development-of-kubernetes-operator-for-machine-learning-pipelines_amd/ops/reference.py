@@ -89,18 +89,36 @@ def fp8_fake_quant(x: torch.Tensor) -> torch.Tensor:
     return fp8_dequantize_rows(*fp8_quantize_rows(x))
 
 
-def rope_cache(qkv, positions, cos_sin, slots, k_cache, v_cache, n_q_heads, k_scale=None, v_scale=None):
+def head_rmsnorm(x, w, eps):
+    """Per-head RMSNorm of fp32 head rows [..., D] with the weight ``w`` [D], no rounding:
+    ``x * rsqrt(mean(x^2) + eps) * w`` (the QK-norm of ``rope_cache``)."""
+    return x * torch.rsqrt(x.pow(2).mean(-1, keepdim=True) + eps) * w.float()
+
+
+def rope_cache(qkv, positions, cos_sin, slots, k_cache, v_cache, n_q_heads, k_scale=None, v_scale=None,
+               q_norm=None, k_norm=None, eps=0.0):
     """Rotate q/k, scatter k/v into the paged cache, return q [T, Hq, D].  An e4m3fn cache takes
     the rows (rounded to the model dtype as a bf16 cache would hold them) quantised by
-    ``fp8_quantize_rows``, their scale bytes going to ``k_scale`` / ``v_scale`` [NB, Hkv, BS]."""
+    ``fp8_quantize_rows``, their scale bytes going to ``k_scale`` / ``v_scale`` [NB, Hkv, BS].
+
+    ``q_norm`` / ``k_norm`` (weights [D], both or neither): per-head QK-norm (Qwen3).  Every q head
+    and every k head x of the row the GEMM stored becomes ``x * rsqrt(mean(x^2) + eps) * w`` in
+    fp32, THEN comes the rotation, and one rounding to the model dtype at the end; V is untouched.
+    transformers rounds to the model dtype between the norm and the rotation; fp32 throughout is
+    this project's convention for RoPE and the more accurate of the two (one rounding, not two)."""
+    if (q_norm is None) != (k_norm is None):
+        raise ValueError("QK-norm needs both q_norm and k_norm")
     T = qkv.shape[0]
     Hkv, BS, D = k_cache.shape[1], k_cache.shape[2], k_cache.shape[3]
     half = D // 2
     x = qkv[:, : (n_q_heads + 2 * Hkv) * D].float().view(T, n_q_heads + 2 * Hkv, D)
     cs = cos_sin[positions.long()].float()  # [T, D]
     cos, sin = cs[:, None, :half], cs[:, None, half:]
-    q = rotate(x[:, :n_q_heads], cos, sin).to(qkv.dtype)
-    k = rotate(x[:, n_q_heads:n_q_heads + Hkv], cos, sin).to(qkv.dtype)
+    xq, xk = x[:, :n_q_heads], x[:, n_q_heads:n_q_heads + Hkv]
+    if q_norm is not None:
+        xq, xk = head_rmsnorm(xq, q_norm, eps), head_rmsnorm(xk, k_norm, eps)
+    q = rotate(xq, cos, sin).to(qkv.dtype)
+    k = rotate(xk, cos, sin).to(qkv.dtype)
     v = x[:, n_q_heads + Hkv:].to(qkv.dtype)
     fp8 = k_cache.dtype == FP8
     if fp8:
