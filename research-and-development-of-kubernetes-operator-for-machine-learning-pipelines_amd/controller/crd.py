@@ -89,6 +89,7 @@ class CanaryPolicy:
 KV_CACHE_DTYPES = ("bf16", "fp8")  # spec.kvCacheDtype (manifests/crd.yaml's enum)
 MAX_SPECULATIVE_TOKENS = 7         # spec.speculativeTokens (manifests/crd.yaml's maximum; runtime/spec.py)
 MAX_GUIDED_STATES = 32767          # spec.guidedDecodingStates (int16 arena entries; runtime/guided.py)
+MAX_EMBEDDING_SLOTS = 4096         # spec.embeddingSlots (manifests/crd.yaml's maximum; EngineConfig.embed_slots)
 
 
 @dataclass(frozen=True)
@@ -114,6 +115,8 @@ class ModelSpec:
     speculative_tokens: int | None = None
     # rows of the LLM runtime's guided-decoding grammar arena: None / 0 = off, up to 32767
     guided_decoding_states: int | None = None
+    # slots of the LLM runtime's embedding pooling accumulator (embedding requests admitted at once): None / 0 = off
+    embedding_slots: int | None = None
 
     @classmethod
     def from_spec(cls, spec: dict) -> "ModelSpec":
@@ -132,7 +135,8 @@ class ModelSpec:
                                   if isinstance(a, dict)),
                    kv_cache_dtype=spec.get("kvCacheDtype"),
                    speculative_tokens=spec.get("speculativeTokens"),
-                   guided_decoding_states=spec.get("guidedDecodingStates"))
+                   guided_decoding_states=spec.get("guidedDecodingStates"),
+                   embedding_slots=spec.get("embeddingSlots"))
 
     def validate(self) -> list[str]:
         errs = []
@@ -173,6 +177,17 @@ class ModelSpec:
                 errs.append(f"spec.guidedDecodingStates must be an integer in [0, {MAX_GUIDED_STATES}], not {g!r}")
             elif g > 0 and (int(self.tensor_parallel or 1) > 1 or int(self.expert_parallel or 1) > 1):
                 errs.append("spec.guidedDecodingStates needs tensorParallel = 1 and expertParallel = 1")
+        n = self.embedding_slots
+        if n is not None:
+            if isinstance(n, bool) or not isinstance(n, int) or not 0 <= n <= MAX_EMBEDDING_SLOTS:
+                errs.append(f"spec.embeddingSlots must be an integer in [0, {MAX_EMBEDDING_SLOTS}], not {n!r}")
+            elif n > 0:
+                if int(self.tensor_parallel or 1) > 1 or int(self.expert_parallel or 1) > 1:
+                    errs.append("spec.embeddingSlots needs tensorParallel = 1 and expertParallel = 1")
+                if self.speculative_tokens:
+                    errs.append("spec.embeddingSlots is not supported with speculativeTokens")
+                if self.adapters:
+                    errs.append("spec.embeddingSlots is not supported with adapters")
         return errs
 
 

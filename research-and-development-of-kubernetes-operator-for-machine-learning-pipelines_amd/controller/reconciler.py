@@ -292,6 +292,8 @@ class MlflowModelReconciler:
                 engine_args["spec_tokens"] = spec.speculative_tokens  # -> MLOP_ENGINE_SPEC_TOKENS
             if spec.guided_decoding_states and runtime == seldon.RUNTIME_LLM:
                 engine_args["grammar_states"] = spec.guided_decoding_states  # -> MLOP_ENGINE_GRAMMAR_STATES
+            if spec.embedding_slots and runtime == seldon.RUNTIME_LLM:
+                engine_args["embed_slots"] = spec.embedding_slots  # -> MLOP_ENGINE_EMBED_SLOTS
             preds.append(seldon.build_predictor(
                 v, uri, spec.minio_secret, traffic, runtime=runtime, replicas=spec.replicas, placement=placement,
                 image=self.settings.runtime_image, gpu_resource=self.settings.gpu_resource,

@@ -46,6 +46,13 @@ class ModelConfig:
     # per-head QK-norm (Qwen3): an RMSNorm with a learned [head_dim] weight on every q head and
     # every k head between the QKV projection and RoPE (layer weights "q_norm" / "k_norm")
     qk_norm: bool = False
+    # a base-model checkpoint (LlamaModel / MistralModel / Qwen3Model: no LM head; ours is tied to the
+    # embedding table and never asked): it serves embedding requests only.  embed_pooling /
+    # embed_normalize: the request defaults a checkpoint's sentence-transformers settings name
+    # (embed_pooling None: they name a pooling this runtime does not serve, a request must name its own)
+    embedding_only: bool = field(default=False, compare=False)
+    embed_pooling: str | None = field(default="last", compare=False)
+    embed_normalize: bool = field(default=True, compare=False)
 
     @property
     def eos_ids(self) -> tuple:

@@ -36,6 +36,9 @@ from .config import CHECKPOINT_SHAPES, ModelConfig, PRESETS
 # Qwen3 (dense) is the Llama layer with a per-head QK-norm before RoPE (ModelConfig.qk_norm)
 _ARCH_NAMES = {"LlamaForCausalLM": "llama", "MixtralForCausalLM": "mixtral", "MistralForCausalLM": "llama",
                "Qwen3ForCausalLM": "llama"}
+# base-model checkpoints (decoder-style embedding models): the same layers, tensor names without the
+# "model." prefix, no lm_head.weight; they serve embedding requests only (ModelConfig.embedding_only)
+_BASE_ARCHS = {"LlamaModel": "LlamaForCausalLM", "MistralModel": "MistralForCausalLM", "Qwen3Model": "Qwen3ForCausalLM"}
 # GQA groups the attention bindings take (bindings.cpp: decode "GQA group must divide 16"; flash prefill 1, 2, 4, 8)
 _GQA_GROUPS = (1, 2, 4, 8, 16)
 
@@ -78,11 +81,15 @@ def resolve_model_dir(uri: str | None, marker=_is_checkpoint) -> Path | None:
 def config_from_hf(d: dict, name: str | None = None) -> ModelConfig:
     """ModelConfig from an HF ``config.json`` dict (Llama / Mistral / Mixtral / dense Qwen3 families)."""
     arch = (d.get("architectures") or ["LlamaForCausalLM"])[0]
+    embedding_only = arch in _BASE_ARCHS
+    arch = _BASE_ARCHS.get(arch, arch)
     if arch == "Qwen3MoeForCausalLM":
         raise ValueError("Qwen3-MoE checkpoints are not supported: their router (norm_topk_prob, 128 experts) "
                          "differs from Mixtral's; only the dense Qwen3ForCausalLM loads")
     if arch not in _ARCH_NAMES:
-        raise ValueError(f"unsupported checkpoint architecture {arch!r} (supported: {sorted(_ARCH_NAMES)})")
+        raise ValueError(f"unsupported checkpoint architecture {arch!r} (supported: {sorted(_ARCH_NAMES)}, and the "
+                         f"base models {sorted(_BASE_ARCHS)} for embeddings; bidirectional encoders, rerankers and "
+                         "classification heads are not served)")
     if d.get("hidden_act", "silu") != "silu":
         raise ValueError(f"unsupported activation {d.get('hidden_act')!r}")
     H, nh = d["hidden_size"], d["num_attention_heads"]
@@ -131,7 +138,7 @@ def config_from_hf(d: dict, name: str | None = None) -> ModelConfig:
         num_kv_heads=nkv, head_dim=d.get("head_dim") or H // nh,
         rope_theta=float(theta), rms_eps=float(d.get("rms_norm_eps", 1e-5)),
         max_position=max_pos,
-        tie_embeddings=bool(d.get("tie_word_embeddings", False)),
+        tie_embeddings=bool(d.get("tie_word_embeddings", False)) or embedding_only, embedding_only=embedding_only,
         num_experts=int(d.get("num_local_experts", 0) or 0), top_k=int(d.get("num_experts_per_tok", 2)),
         rope_scaling=scaling, eos_token_id=int(eos), extra_eos_ids=eos_all[1:], sliding_window=window,
         qk_norm=qk_norm)
@@ -179,12 +186,14 @@ class HFWeights:
         self.cfg = cfg
         t = _Tensors(path)
         self._t = t
-        self.embed = t.get("model.embed_tokens.weight")
-        self.final_norm = t.get("model.norm.weight")
+        # a base-model checkpoint (LlamaModel / MistralModel / Qwen3Model) names its tensors without "model."
+        pre = "model." if t.has("model.embed_tokens.weight") or not t.has("embed_tokens.weight") else ""
+        self.embed = t.get(pre + "embed_tokens.weight")
+        self.final_norm = t.get(pre + "norm.weight")
         self.lm_head = t.get("lm_head.weight") if t.has("lm_head.weight") else self.embed
 
         def layer(i):
-            p = f"model.layers.{i}."
+            p = f"{pre}layers.{i}."
             L = {"qkv": lambda: torch.cat([t.get(p + f"self_attn.{n}_proj.weight") for n in "qkv"], 0),
                  "o": lambda: t.get(p + "self_attn.o_proj.weight"),
                  "in_norm": lambda: t.get(p + "input_layernorm.weight"),
@@ -220,6 +229,27 @@ class HFWeights:
         self.layers = [layer(i) for i in range(cfg.num_layers)]
 
 
+def embedding_defaults(path: str | os.PathLike) -> tuple:
+    """(pooling, normalize) an embedding request to the checkpoint in ``path`` gets when it names none:
+    from its sentence-transformers settings (``modules.json`` lists the modules, a ``Normalize`` one
+    among them or not; ``1_Pooling/config.json`` holds the pooling mode), ("last", True) without
+    them.  A pooling mode this runtime does not serve (CLS, max, weighted mean, ...) gives None: a
+    request must then name its pooling."""
+    path = Path(path)
+    mods, pool = path / "modules.json", path / "1_Pooling" / "config.json"
+    if not mods.is_file() and not pool.is_file():
+        return "last", True
+    normalize = False
+    if mods.is_file():
+        normalize = any(str(m.get("type", "")).endswith("Normalize") for m in json.loads(mods.read_text()))
+    pooling = None
+    if pool.is_file():
+        pc = json.loads(pool.read_text())
+        on = sorted(k for k, v in pc.items() if k.startswith("pooling_mode_") and v is True)
+        pooling = {("pooling_mode_lasttoken",): "last", ("pooling_mode_mean_tokens",): "mean"}.get(tuple(on))
+    return pooling, normalize
+
+
 def load_pretrained(path: str | os.PathLike, device="cuda", dtype=torch.bfloat16, pstate=None,
                     name: str | None = None, fold_norms: bool = True):
     """Build our model for the checkpoint in ``path`` and copy its (TP-sharded) weights in."""
@@ -227,6 +257,8 @@ def load_pretrained(path: str | os.PathLike, device="cuda", dtype=torch.bfloat16
 
     path = Path(path)
     cfg = config_from_hf(json.loads((path / "config.json").read_text()), name=name or path.name)
+    pooling, normalize = embedding_defaults(path)
+    cfg = replace(cfg, embed_pooling=pooling, embed_normalize=normalize)
     model = build_model(cfg, device=device, dtype=dtype, pstate=pstate)
     with torch.no_grad():
         model.load_shard_from(HFWeights(path, cfg))

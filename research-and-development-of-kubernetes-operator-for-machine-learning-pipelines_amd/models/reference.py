@@ -34,7 +34,14 @@ def _mlp(model, i, x):
 
 @torch.no_grad()
 def dense_logits(model, tokens, kv_cache_dtype: str | None = None) -> torch.Tensor:
-    """[T, V] fp32 logits of a single sequence (TP=1 models only).  ``kv_cache_dtype="fp8"``: the
+    """[T, V] fp32 logits of a single sequence (TP=1 models only): the LM head over ``dense_hidden``."""
+    return F.linear(dense_hidden(model, tokens, kv_cache_dtype), model.lm_head.float())
+
+
+@torch.no_grad()
+def dense_hidden(model, tokens, kv_cache_dtype: str | None = None) -> torch.Tensor:
+    """[T, H] fp32 final-normed hidden states of a single sequence (TP=1 models only): what the LM
+    head and the embedding pooling read.  ``kv_cache_dtype="fp8"``: the
     post-RoPE K and the V rows go through the fp8 KV cache's format per (token, kv head)
     (``ops.reference.fp8_fake_quant``), the oracle of an engine with that cache; None / "bf16":
     no quantisation."""
@@ -76,4 +83,4 @@ def dense_logits(model, tokens, kv_cache_dtype: str | None = None) -> torch.Tens
         res = res + _mlp(model, i, x)
         nxt = model.layers[i + 1]["in_norm"] if i + 1 < len(model.layers) else model.final_norm
         x = ref.rmsnorm(res, nxt.float(), cfg.rms_eps)
-    return F.linear(x, model.lm_head.float())
+    return x

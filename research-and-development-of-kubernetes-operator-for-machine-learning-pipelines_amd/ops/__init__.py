@@ -902,8 +902,40 @@ def spec_propose(hist, hist_len, rows, cap, n_max: int, n_min: int, out) -> None
     torch.ops.mlop.spec_propose(hist, hist_len, rows, cap, int(n_max), int(n_min), out)
 
 
+# embedding pooling: flag bits of a segment row [r0, r1, slot, flags] and a finish row [slot, count, d, flags]
+POOL_INIT, POOL_LAST, POOL_MODE_LAST = ref.POOL_INIT, ref.POOL_LAST, ref.POOL_MODE_LAST
+POOL_FIN_NORMALIZE, POOL_FIN_MEAN = ref.POOL_FIN_NORMALIZE, ref.POOL_FIN_MEAN
+
+
+def pool_accumulate(x: torch.Tensor, seg: torch.Tensor, acc: torch.Tensor, nseg: int | None = None) -> None:
+    """In place on ``acc`` fp32 [slots, H]: the pool segments ``seg`` (int32 [>= nseg, 4]) over the rows
+    of the hidden states ``x`` [T, H] (bf16), ``reference.pool_reference``: a ``mean`` segment adds
+    its rows to its slot one by one in fp32 (from 0 under POOL_INIT), a POOL_MODE_LAST segment with
+    POOL_LAST copies its last row.  Rows outside every segment are not read, other slots not written."""
+    nseg = seg.shape[0] if nseg is None else int(nseg)
+    if not acc.is_cuda:
+        acc.copy_(ref.pool_reference(x, seg[:nseg], acc)[0])
+        return
+    _need_gpu()
+    torch.ops.mlop.pool_accumulate(acc, x, seg, nseg)
+
+
+def pool_finish(acc: torch.Tensor, fin: torch.Tensor, out: torch.Tensor, nfin: int | None = None) -> None:
+    """out[slot, :d] (fp32) = the finished vector of every row [slot, count, d, flags] of ``fin`` (int32
+    [>= nfin, 4]): acc[slot, :d] / count under POOL_FIN_MEAN, L2-normalised (v / max(||v||, 1e-12))
+    under POOL_FIN_NORMALIZE.  Other slots, and columns from d on, keep what they held."""
+    nfin = fin.shape[0] if nfin is None else int(nfin)
+    if not acc.is_cuda:
+        res = ref.pool_reference(acc[:0, :0], [], acc, fin[:nfin])[1]
+        for slot, _, d, _ in fin[:nfin].tolist():
+            out[slot, :d] = res[slot, :d].float()
+        return
+    _need_gpu()
+    torch.ops.mlop.pool_finish(out, acc, fin, nfin)
+
+
 __all__ = ["argmax", "sample", "penalty_table", "penalty_reset", "penalty_update", "apply_penalties",
-           "token_logprobs", "grammar_arena", "grammar_mask", "grammar_advance", "spec_accept", "spec_propose", "load","available", "library_path", "rmsnorm", "add_rmsnorm", "rope_cache",
+           "token_logprobs", "grammar_arena", "grammar_mask", "grammar_advance", "spec_accept", "spec_propose", "pool_accumulate", "pool_finish", "load","available", "library_path", "rmsnorm", "add_rmsnorm", "rope_cache",
            "silu_mul", "embedding", "paged_attention", "ref"]
 
 

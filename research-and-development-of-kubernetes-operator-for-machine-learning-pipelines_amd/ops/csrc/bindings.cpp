@@ -928,6 +928,43 @@ void spec_propose(Tensor hist, Tensor hist_len, Tensor rows, Tensor cap, int64_t
                             out.data_ptr<int>(), (int)k, (int)rows.numel(), cur_stream());
 }
 
+// embedding pooling (pool.hip): seg int32 [>= nseg, 4] = [r0, r1, slot, flags], acc fp32 [S, H]
+static void check_pool_state(const Tensor& acc, const Tensor& meta, int64_t n, const char* name) {
+  TORCH_CHECK(acc.is_cuda() && acc.scalar_type() == at::kFloat && acc.dim() == 2 && acc.is_contiguous(),
+              "acc must be a contiguous fp32 GPU tensor [slots, H]");
+  TORCH_CHECK(acc.size(1) % 8 == 0 && acc.size(1) <= 65536 && acc.size(0) <= INT_MAX,
+              "hidden size must be a multiple of 8");
+  TORCH_CHECK((uintptr_t)acc.data_ptr() % 16 == 0, "acc must be 16-byte aligned");
+  check_i32(meta, name);
+  TORCH_CHECK(meta.dim() == 2 && meta.size(1) == 4 && n >= 0 && n <= meta.size(0) && n <= 65535, name,
+              " must be int32 [n, 4] with n <= 65535");
+  TORCH_CHECK((uintptr_t)meta.data_ptr() % 16 == 0, name, " must be 16-byte aligned");
+  TORCH_CHECK(meta.device() == acc.device(), name, " must be on acc's device");
+}
+
+void pool_accumulate(Tensor acc, Tensor x, Tensor seg, int64_t nseg) {
+  check_pool_state(acc, seg, nseg, "seg");
+  const int64_t H = acc.size(1);
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 && x.dim() == 2 && x.size(1) == H &&
+                  (x.size(0) == 0 || x.stride(1) == 1) && x.stride(0) >= H && x.stride(0) % 8 == 0,
+              "x must be bf16 [T, H] with unit column stride and a row stride that is a multiple of 8");
+  TORCH_CHECK((uintptr_t)x.data_ptr() % 16 == 0 && x.size(0) <= INT_MAX, "x must be 16-byte aligned");
+  TORCH_CHECK(x.device() == acc.device(), "x must be on acc's device");
+  c10::DeviceGuard g(acc.device());
+  mlop::launch_pool_accumulate(acc.data_ptr<float>(), x.data_ptr(), x.stride(0), seg.data_ptr<int>(), (int)nseg,
+                               (int)x.size(0), (int)H, (int)acc.size(0), cur_stream());
+}
+
+void pool_finish(Tensor out, Tensor acc, Tensor fin, int64_t nfin) {
+  check_pool_state(acc, fin, nfin, "fin");
+  TORCH_CHECK(out.is_cuda() && out.scalar_type() == at::kFloat && out.dim() == 2 && out.is_contiguous() &&
+                  out.size(0) == acc.size(0) && out.size(1) == acc.size(1) && out.device() == acc.device(),
+              "out must be a contiguous fp32 GPU tensor of acc's shape");
+  c10::DeviceGuard g(acc.device());
+  mlop::launch_pool_finish(out.data_ptr<float>(), out.size(1), acc.data_ptr<float>(), fin.data_ptr<int>(), (int)nfin,
+                           (int)acc.size(1), (int)acc.size(0), cur_stream());
+}
+
 void apply_penalties(Tensor logits, Tensor table, Tensor slots, Tensor rep, Tensor freq, Tensor pres) {
   check_logits(logits);
   check_table(table);
@@ -1256,6 +1293,8 @@ TORCH_LIBRARY(mlop, m) {
         "Tensor(b!) hist_len, Tensor(c!) out) -> ()");
   m.def("spec_propose(Tensor hist, Tensor hist_len, Tensor rows, Tensor cap, int n_max, int n_min, "
         "Tensor(a!) out) -> ()");
+  m.def("pool_accumulate(Tensor(a!) acc, Tensor x, Tensor seg, int nseg) -> ()");
+  m.def("pool_finish(Tensor(a!) out, Tensor acc, Tensor fin, int nfin) -> ()");
   m.def("rmsnorm(Tensor(a!) out, Tensor x, Tensor w, float eps) -> ()");
   m.def("add_rmsnorm(Tensor(a!) out, Tensor(b!) residual, Tensor x, Tensor w, float eps) -> ()");
   m.def("rope_cache(Tensor(a!) q_out, Tensor(b!) k_cache, Tensor(c!) v_cache, Tensor qkv, "
@@ -1325,6 +1364,8 @@ TORCH_LIBRARY_IMPL(mlop, CUDA, m) {
   m.impl("token_logprobs", &token_logprobs);
   m.impl("spec_accept", &spec_accept);
   m.impl("spec_propose", &spec_propose);
+  m.impl("pool_accumulate", &pool_accumulate);
+  m.impl("pool_finish", &pool_finish);
   m.impl("car_all_reduce", &car_all_reduce);
   m.impl("car_all_reduce_add", &car_all_reduce_add);
   m.impl("car_broadcast", &car_broadcast);

@@ -219,6 +219,14 @@ void launch_spec_accept(const long* sampled, int T, const int* q_start, const in
                         int B, hipStream_t st);
 void launch_spec_propose(const int* hist, long ld, int max_len, const int* hist_len, int R, const int* rows,
                          const int* cap, int n_max, int n_min, int* out, int k, int B, hipStream_t st);
+// embedding pooling (pool.hip).  seg int32 [nseg, 4] = [r0, r1, slot, flags] over the rows of x[T, ldx] (bf16),
+// acc fp32 [S, H]; fin int32 [nfin, 4] = [slot, count, d, flags], out fp32 [S, ldo >= H]; H % 8 == 0
+constexpr int kPoolInit = 1, kPoolLast = 2, kPoolModeLast = 4;  // segment flags
+constexpr int kPoolFinNormalize = 1, kPoolFinMean = 2;          // finish flags
+void launch_pool_accumulate(float* acc, const void* x, long ldx, const int* seg, int nseg, int T, int H, int S,
+                            hipStream_t st);
+void launch_pool_finish(float* out, long ldo, const float* acc, const int* fin, int nfin, int H, int S,
+                        hipStream_t st);
 
 // lazily backed KV arenas (vmm.hip): reserve VA, back chunks synchronously or on a native
 // worker thread; the returned owner must outlive every use of the range

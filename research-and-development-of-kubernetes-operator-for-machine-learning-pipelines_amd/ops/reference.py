@@ -280,3 +280,42 @@ def lora_expand_add(y, tmp, B, tile_group, tok_slot, slot_rank=None):
             acc[:, cols] += tmp[rows, g * R:(g + 1) * R] @ B[s][cols].float().t()
         y[rows] = acc.to(y.dtype)
     return y
+
+
+# -------------------------------------------------------------- pooling --
+# Embedding pooling (csrc/pool.hip).  Segment rows [r0, r1, slot, flags], finish rows
+# [slot, count, d, flags]; the flag bits are those of csrc/launch.h.
+POOL_INIT, POOL_LAST, POOL_MODE_LAST = 1, 2, 4
+POOL_FIN_NORMALIZE, POOL_FIN_MEAN = 1, 2
+
+
+def pool_reference(x, seg, acc, fin=None):
+    """The contract of ``ops.pool_accumulate`` / ``ops.pool_finish``.
+
+    ``x`` [T, H] (bf16), ``seg`` int [nseg, 4], ``acc`` fp32 [S, H], ``fin`` int [nfin, 4] or None.
+    Returns (acc', out): acc' = a copy of ``acc`` after the segments, in order.  A ``mean``
+    segment: acc'[slot] = (0 if POOL_INIT else acc'[slot]) + x[r0] + ... + x[r1 - 1], one fp32 add
+    per row, the rows strictly in order.  A POOL_MODE_LAST segment writes float(x[r1 - 1]) if it
+    carries POOL_LAST and nothing otherwise.  out: float64 [S, H], zero but for the finished slots'
+    first d columns: v = acc'[slot, :d] / count (POOL_FIN_MEAN only), then v / max(||v||, 1e-12)
+    under POOL_FIN_NORMALIZE, all in float64 from the exact fp32 sums."""
+    acc = acc.detach().to("cpu", torch.float32).clone()
+    xs = x.detach().to("cpu")
+    for r0, r1, slot, flags in torch.as_tensor(seg).reshape(-1, 4).tolist():
+        if flags & POOL_MODE_LAST:
+            if flags & POOL_LAST:
+                acc[slot] = xs[r1 - 1].float()
+            continue
+        a = torch.zeros_like(acc[slot]) if flags & POOL_INIT else acc[slot].clone()
+        for r in range(r0, r1):
+            a = a + xs[r].float()
+        acc[slot] = a
+    out = torch.zeros(acc.shape, dtype=torch.float64)
+    for slot, count, d, flags in (torch.as_tensor(fin).reshape(-1, 4).tolist() if fin is not None else ()):
+        v = acc[slot, :d].double()
+        if flags & POOL_FIN_MEAN:
+            v = v / count
+        if flags & POOL_FIN_NORMALIZE:
+            v = v / max(float(v.square().sum().sqrt()), 1e-12)
+        out[slot, :d] = v
+    return acc, out

@@ -128,7 +128,8 @@ class LLMBackend:
             now = time.perf_counter()
             self.ktime.after_step(now)
             if self.metrics:
-                self.metrics.mark_step(len(outs), now)
+                # (a delivered embedding is a StepOutput without a token: not in the token rate)
+                self.metrics.mark_step(sum(o.embedding is None for o in outs), now)
             for o in outs:
                 r = self._active.get(o.seq_id)
                 if r is None:
@@ -138,6 +139,17 @@ class LLMBackend:
                     if self.metrics:
                         self.metrics.ttft.labels(**self.metrics.labels).observe(now - r.t0)
                         self.metrics.tokens_in.labels(**self.metrics.labels).inc(len(r.prompt))
+                if o.embedding is not None:
+                    # an embedding request: no token, one vector
+                    self._active.pop(o.seq_id, None)
+                    if r.queue is not None:  # (the server refuses to stream one; a caller of submit() may)
+                        r.loop.call_soon_threadsafe(r.queue.put_nowait, None)
+                    if self.metrics:
+                        self.metrics.mark_embedding(len(r.prompt))
+                    r.loop.call_soon_threadsafe(_set_res, r.future, {
+                        "embedding": o.embedding, "finish_reason": o.finish_reason, "latency": now - r.t0,
+                        "prompt_tokens": len(r.prompt)})
+                    continue
                 r.tokens.append(o.token)
                 item = o.token
                 if r.logprobs is not None:
@@ -182,8 +194,32 @@ class LLMBackend:
     async def generate(self, prompt_ids, params: SamplingParams) -> dict:
         return await self.submit(prompt_ids, params).future
 
+    async def embed(self, prompts, params: SamplingParams) -> list:
+        """One engine request per prompt (a list of token ids each) with the embedding parameters
+        ``params``; resolves to their results ({"embedding": np.float32 [d], "prompt_tokens", ...}, in
+        order) when all have their vectors."""
+        reqs = [self.submit(p, params) for p in prompts]
+        return list(await asyncio.gather(*(r.future for r in reqs)))
+
+    def embedding_defaults(self) -> tuple:
+        """(pooling or None, normalize) of a request that names none: the checkpoint's own settings."""
+        cfg = self.engine.model.cfg
+        return getattr(cfg, "embed_pooling", "last"), bool(getattr(cfg, "embed_normalize", True))
+
+    @property
+    def embedding_only(self) -> bool:
+        """The model is a base-model checkpoint without an LM head: every request is an embedding request."""
+        return bool(getattr(self.engine.model.cfg, "embedding_only", False))
+
+    @property
+    def serves_embeddings(self) -> bool:
+        return bool(getattr(getattr(self.engine, "cfg", None), "embed_slots", 0))
+
     def check_params(self, params: SamplingParams) -> None:
         """ValueError (HTTP 400) for what this predictor cannot serve: an adapter it has not loaded."""
+        if params.embed is not None and not self.serves_embeddings:
+            raise ValueError("this predictor serves no embedding requests (embeddingSlots / embed_slots = 0; "
+                             "not available on tensor- or expert-parallel predictors)")
         if params.adapter is not None and params.adapter not in getattr(self.engine, "_adapters", {}):
             raise ValueError(f"unknown adapter {params.adapter!r}")
         if params.guided is not None:
@@ -212,6 +248,12 @@ class LLMBackend:
             md["guided_decoding"] = True
             md["grammar_states"] = int(self.engine.cfg.grammar_states)
             md["grammar_arena_bytes"] = int(self.engine.stats.get("grammar_arena_bytes", 0))
+        if self.serves_embeddings:  # (likewise)
+            pooling, normalize = self.embedding_defaults()
+            md["embeddings"] = {"slots": int(self.engine.cfg.embed_slots), "dimensions": int(cfg.hidden_size),
+                                "default_pooling": pooling, "default_normalize": normalize,
+                                "embedding_only": self.embedding_only}
+            md["outputs"] = md["outputs"] + [{"name": "embedding", "datatype": "FP32", "shape": [-1, int(cfg.hidden_size)]}]
         return md
 
 

@@ -29,6 +29,12 @@ Step policy:
     a list of choices or a JSON schema: its compiled token table lives in a device arena, its
     automaton state in a device vector indexed by engine row; the sampler masks the row's logits
     by the state before the draw and advances the state behind it, so the host never reads it.
+  * with ``embed_slots`` > 0 a request may ask for an EMBEDDING (``SamplingParams.embed``): a
+    prefill-only sequence.  Its prompt is chunked like any other, in prompt-only and mixed steps;
+    behind the forward of every step that carries one of its chunks ops.pool_accumulate pools the
+    chunk's hidden states into the sequence's slot of an fp32 accumulator, and behind its last
+    chunk ops.pool_finish scales / truncates / normalises the vector.  It gets no logits row, never
+    joins the running rows and gives its pages and row back with its last chunk's launch.
 """
 from __future__ import annotations
 
@@ -196,6 +202,8 @@ class Sequence:
     prefix_seed: bytes = b""                    # seed of the prefix hash chain: the adapter's identity
     grammar: object = None                      # guided decoding: the compiled guided.Grammar (pinned)
     g_admitted: bool = False                    # ... and whether the sequence's row holds a reference on its arena range
+    emb_slot: int = -1                          # embedding request: its accumulator slot, held until the vector is delivered
+    embedding: object = None                    # ... and the vector (np.float32 [d]) once it is
 
     @property
     def length(self) -> int:
@@ -267,6 +275,11 @@ class EngineConfig:
     # request is refused.  Not with tensor or expert parallelism.
     grammar_states: int = 0
     grammar_cache: int = 16
+    # embedding requests (SamplingParams.embed): slots of the fp32 pooling accumulator ([embed_slots,
+    # hidden] plus an output buffer and its pinned mirror) = embedding sequences admitted at once;
+    # further ones wait for a slot.  0 = off: nothing is allocated and such a request is refused.
+    # Not with tensor or expert parallelism, speculation, LoRA slots or MoE models.
+    embed_slots: int = 0
 
 
 @dataclass
@@ -277,6 +290,7 @@ class StepOutput:
     finish_reason: str | None = None
     logprob: float | None = None        # SamplingParams.logprobs: the token's log-probability
     top_logprobs: list | None = None    # ... and the top-N [(id, logprob), ...]
+    embedding: np.ndarray | None = None  # an embedding request's vector (fp32 [d]): token -1, reason "embedding"
 
 
 class _ParamsList(list):
@@ -304,10 +318,14 @@ class _Step:
 
     A speculative verify step (``nd`` not None) feeds decode row i its last token and ``nd[i]`` of
     ``drafts[i]``: its ``nlog`` logits rows are the rows' tokens in order, row i's from ``q0[i]``,
-    ``srows`` the engine row and ``goff`` the offset inside its row of each."""
+    ``srows`` the engine row and ``goff`` the offset inside its row of each.
+
+    Embedding sequences of ``batch``: ``emb_done`` (its prompt completes; such a sequence is never in
+    ``done`` / ``done_seqs``) and, once ``_chunks_done`` ran, ``emb_out``: the (sequence, slot, d) whose
+    vectors this step finishes."""
 
     __slots__ = ("rows", "ctx_d", "B", "batch", "chunks", "p_ctx", "done", "done_seqs", "srows", "seqs",
-                 "T", "launch", "params", "greedy", "nd", "drafts", "q0", "goff", "nlog")
+                 "T", "launch", "params", "greedy", "nd", "drafts", "q0", "goff", "nlog", "emb_done", "emb_out")
 
 
 class _Pending:
@@ -317,21 +335,23 @@ class _Pending:
     (``lp``: pinned values, pinned ids, the rows' wanted counts; or None) and ``retire``, the ids
     of the sequences whose pending token is their last."""
 
-    __slots__ = ("rows", "epochs", "seqs", "toks_d", "toks_h", "ev", "lp", "retire")
+    __slots__ = ("rows", "epochs", "seqs", "toks_d", "toks_h", "ev", "lp", "retire", "emb")
 
-    def __init__(self, rows, epochs, seqs, toks_d, toks_h, ev, lp):
+    def __init__(self, rows, epochs, seqs, toks_d, toks_h, ev, lp, emb=()):
         self.rows, self.epochs, self.seqs, self.toks_d, self.toks_h = rows, epochs, seqs, toks_d, toks_h
         self.ev, self.lp, self.retire = ev, lp, set()
+        self.emb = emb  # (sequence, slot, d) of the embeddings the step finishes (pinned mirror, behind ev)
 
 
 class StepBatch:
     """One step's outputs as arrays (no per-token Python objects on the hot path);
     iterating yields ``StepOutput`` lazily."""
 
-    __slots__ = ("seq_ids", "tokens", "fin", "reasons", "lps")
+    __slots__ = ("seq_ids", "tokens", "fin", "reasons", "lps", "embs")
 
-    def __init__(self, seq_ids, tokens, fin, reasons: dict, lps: dict | None = None):
+    def __init__(self, seq_ids, tokens, fin, reasons: dict, lps: dict | None = None, embs: dict | None = None):
         self.seq_ids, self.tokens, self.fin, self.reasons = seq_ids, tokens, fin, reasons
+        self.embs = embs or None  # seq_id -> vector of the embedding requests that finished
         # seq_id -> (logprob, [(id, logprob), ...]) of the rows that asked for log-probabilities
         # (a sequence has at most one token per step); None when no row did
         self.lps = lps or None
@@ -342,7 +362,8 @@ class StepBatch:
                    np.array([o.token for o in outs], dtype=np.int64),
                    np.array([o.finished for o in outs], dtype=bool),
                    {o.seq_id: o.finish_reason for o in outs if o.finished},
-                   {o.seq_id: (o.logprob, o.top_logprobs) for o in outs if o.logprob is not None})
+                   {o.seq_id: (o.logprob, o.top_logprobs) for o in outs if o.logprob is not None},
+                   {o.seq_id: o.embedding for o in outs if o.embedding is not None})
 
     @classmethod
     def concat(cls, a: "StepBatch", b: "StepBatch"):
@@ -352,15 +373,17 @@ class StepBatch:
         if a.lps or b.lps:
             lps = dict(a.lps or {})
             lps.update(b.lps or {})
+        embs = {**(a.embs or {}), **(b.embs or {})}
         return cls(np.concatenate([a.seq_ids, b.seq_ids]), np.concatenate([a.tokens, b.tokens]),
-                   np.concatenate([a.fin, b.fin]), reasons, lps)
+                   np.concatenate([a.fin, b.fin]), reasons, lps, embs)
 
     def __len__(self):
         return len(self.seq_ids)
 
     def _out(self, sid, tok, f):
         lp = self.lps.get(sid) if self.lps else None
-        return StepOutput(sid, tok, f, self.reasons.get(sid) if f else None, *(lp or ()))
+        return StepOutput(sid, tok, f, self.reasons.get(sid) if f else None, *(lp or (None, None)),
+                          self.embs.get(sid) if self.embs else None)
 
     def __iter__(self):
         for sid, tok, f in zip(self.seq_ids.tolist(), self.tokens.tolist(), self.fin.tolist()):
@@ -411,6 +434,8 @@ class Engine:
         # the KV pool is sized from what is left
         self.stats = collections.Counter()
         self._guided_init(cfg, model)
+        # embedding requests: the pooling accumulator, likewise ahead of the KV pool
+        self._embed_init(cfg, model)
         nb = cfg.num_kv_blocks or self._auto_blocks()
         tp = model.ps.tp
         self.step_sync = StepSync(tp, model.ps.tp_cpu) if tp.size > 1 else None
@@ -834,6 +859,111 @@ class Engine:
         self.r_gbase[r] = g.base
         return True
 
+    # ------------------------------------------------------- embeddings --
+    def _embed_init(self, cfg, model):
+        """The pooling state of an engine that serves embedding requests: the fp32 accumulator and
+        the finished vectors ([embed_slots, H] each), the pinned mirror the vectors come back
+        through, and a step's segment / finish rows (int32 [2 embed_slots, 4]: a step carries at
+        most one chunk per slot) on both sides of their H2D."""
+        n = cfg.embed_slots
+        self._pool_acc = None
+        self._free_embed: list = []
+        self._step_pool = None  # the step being launched: (segments, finish rows, [(slot, d)]) or None
+        if not n:
+            return
+        if isinstance(n, bool) or not isinstance(n, int) or not 0 < n <= 65535:
+            raise ValueError(f"embed_slots must be an int in [0, 65535], got {n!r}")
+        if model.ps.tp.size > 1 or model.ps.ep.size > 1:
+            raise ValueError("embed_slots > 0 is not supported with tensor or expert parallelism "
+                             "(the pooled rows would need the segment metadata on every rank)")
+        if self.spec_k:
+            raise ValueError("embed_slots > 0 is not supported on a speculative engine (spec_tokens > 0)")
+        if cfg.max_adapters > 0:
+            raise ValueError("embed_slots > 0 is not supported with LoRA adapters (max_adapters > 0)")
+        if getattr(model.cfg, "is_moe", False):
+            raise ValueError("embed_slots > 0 is not supported for MoE models")
+        H, dev = model.cfg.hidden_size, self.device
+        if H % 8:
+            raise ValueError(f"embed_slots > 0 needs a hidden size that is a multiple of 8, got {H}")
+        cuda = dev.type == "cuda"
+        self._pool_acc = torch.zeros(n, H, dtype=torch.float32, device=dev)
+        self._pool_out = torch.zeros(n, H, dtype=torch.float32, device=dev)
+        self._pool_out_h = torch.zeros(n, H, dtype=torch.float32, pin_memory=cuda)
+        self._pool_h = torch.zeros(2 * n, 4, dtype=torch.int32, pin_memory=cuda)
+        self._pool_hn = self._pool_h.numpy()
+        self._pool_d = torch.zeros(2 * n, 4, dtype=torch.int32, device=dev)
+        self._free_embed = list(range(n - 1, -1, -1))
+        self.stats["embed_bytes"] = 2 * n * H * 4
+        for key in ("embed_requests", "embed_tokens", "embed_steps"):
+            self.stats[key] = 0
+
+    def _fill_pool(self, st: _Step) -> None:
+        """The step's pool segments and finish rows into the pinned buffer (rewritten only after
+        ``_wait_meta``, like the metadata): one segment per embedding sequence of ``st.batch``, its
+        chunk's rows in the step's token order (the decode rows, then each prompt chunk).  Leaves
+        ``_step_pool`` (None: the step carries no embedding chunk)."""
+        self._step_pool = None
+        if self._pool_acc is None or not any(s.params.embed is not None for s in st.batch):
+            return
+        S = self.cfg.embed_slots
+        seg, fin = self._pool_hn[:S], self._pool_hn[S:]
+        H = self.model.cfg.hidden_size
+        t, ns, fins = st.B, 0, []
+        for s, n, c, e in zip(st.batch, st.chunks, st.p_ctx, st.emb_done):
+            p = s.params
+            if p.embed is not None:
+                mean = p.embed == "mean"
+                flags = (0 if mean else ops.POOL_MODE_LAST) | (ops.POOL_LAST if e else 0)
+                if c - n == 0:  # the first computed chunk (again after preemption): overwrite the slot
+                    flags |= ops.POOL_INIT
+                seg[ns] = (t, t + n, s.emb_slot, flags)
+                ns += 1
+                self.stats["embed_tokens"] += n
+                if e:
+                    d = p.embed_dim or H
+                    f_flags = (ops.POOL_FIN_MEAN if mean else 0) | (ops.POOL_FIN_NORMALIZE if p.embed_normalize else 0)
+                    fin[len(fins)] = (s.emb_slot, s.length, d, f_flags)  # (mean: over the sequence's own tokens)
+                    fins.append((s.emb_slot, d))
+            t += n
+        self._step_pool = (ns, len(fins), fins)
+
+    def _pool_run(self, hidden) -> None:
+        """Behind a step's forward, on its stream: pool the step's segments, finish the vectors that
+        completed and start their copies to the pinned mirror (a slot's row of the mirror belongs
+        to its sequence until the vector is delivered)."""
+        ns, nf, fins = self._step_pool
+        S = self.cfg.embed_slots
+        cuda = self.device.type == "cuda"
+        ops.pool_accumulate(hidden, self._pool_d[:S], self._pool_acc, ns)
+        if nf:
+            ops.pool_finish(self._pool_acc, self._pool_d[S:], self._pool_out, nf)
+            for slot, d in fins:
+                self._pool_out_h[slot, :d].copy_(self._pool_out[slot, :d], non_blocking=cuda)
+        self.stats["embed_steps"] += 1
+
+    def _deliver_embeds(self, emb) -> list:
+        """StepOutputs of the embeddings a step finished, once its copies to the pinned mirror have
+        executed; a sequence aborted meanwhile (its slot freed, maybe re-taken) is dropped."""
+        outs = []
+        for s, slot, d in emb:
+            if s.status == Status.FINISHED or s.emb_slot != slot:
+                continue
+            s.embedding = self._pool_out_h[slot, :d].numpy().copy()
+            if s.first_token_time is None:
+                s.first_token_time = time.perf_counter()
+            self._finish(s, "embedding")
+            self.stats["embed_requests"] += 1
+            outs.append(StepOutput(s.seq_id, -1, True, "embedding", embedding=s.embedding))
+        return outs
+
+    def embed(self, prompts, pooling: str = "last", normalize: bool = True, dim: int | None = None) -> list:
+        """Offline batch API beside ``generate``: one fp32 vector (np.ndarray [dim or hidden]) per prompt."""
+        sp = SamplingParams(embed=pooling, embed_normalize=normalize, embed_dim=dim)
+        seqs = [self.add_request(p, sp) for p in prompts]
+        while any(s.status != Status.FINISHED for s in seqs):
+            self.step()
+        return [s.embedding for s in seqs]
+
     # ----------------------------------------------------------- sizing --
     def _auto_blocks(self) -> int:
         mc, m = self.model.cfg, self.model
@@ -864,7 +994,9 @@ class Engine:
         ids outside the vocabulary, unusable sampling parameters)."""
         if not prompt:
             raise ValueError("empty prompt")
-        if len(prompt) >= self.max_model_len:
+        # (a generation prompt needs room for one token; an embedding input may fill the context)
+        embed = params is not None and params.embed is not None
+        if len(prompt) >= self.max_model_len + int(embed):
             raise ValueError(f"prompt of {len(prompt)} tokens exceeds max_model_len {self.max_model_len}")
         V = self.model.cfg.vocab_size
         if min(prompt) < 0 or max(prompt) >= V:
@@ -876,6 +1008,16 @@ class Engine:
             raise ValueError(f"unknown adapter {params.adapter!r} (loaded: {sorted(self._adapters)})")
         if params.guided is not None:
             self.compile_guided(params)  # compiles it (or finds it in the cache): ValueError for a bad one
+        if params.embed is None:
+            if getattr(self.model.cfg, "embedding_only", False):
+                raise ValueError("this model serves embeddings only (a base-model checkpoint without an LM head): "
+                                 "the request must name a pooling mode")
+            return
+        if self._pool_acc is None:
+            raise ValueError("this engine serves no embedding requests (embed_slots = 0)")
+        H = self.model.cfg.hidden_size
+        if params.embed_dim is not None and params.embed_dim > H:
+            raise ValueError(f"embed_dim must be in [1, {H}] (the model's hidden size), got {params.embed_dim}")
 
     def add_request(self, prompt, params: SamplingParams | None = None, seq_id: int | None = None) -> Sequence:
         params = params or SamplingParams()
@@ -1033,6 +1175,11 @@ class Engine:
         seq.finish_reason = reason
         seq.finish_time = time.perf_counter()
         self._release(seq)
+        if seq.emb_slot >= 0:
+            # (kept across preemption; an in-flight step that still writes the slot is ahead of
+            # the next owner's first chunk on the stream)
+            self._free_embed.append(seq.emb_slot)
+            seq.emb_slot = -1
         if seq.slot >= 0:  # the adapter may be unloaded once no live sequence names it
             self._slot_refs[seq.slot] -= 1
             seq.slot = -1
@@ -1145,14 +1292,21 @@ class Engine:
             batch.append(seq)
             chunks.append(n)
             budget -= n
-        while budget > 0 and self.waiting and self.free_rows:
-            seq = self.waiting[0]
+        skip = 0  # embedding requests at the head of the queue that wait for a slot: those behind go on
+        while budget > 0 and len(self.waiting) > skip and self.free_rows:
+            seq = self.waiting[skip]
+            if seq.params.embed is not None and seq.emb_slot < 0:
+                if not self._free_embed:
+                    skip += 1
+                    continue
+                seq.emb_slot = self._free_embed.pop()
             seq.row = self.free_rows.pop()
             self.rows_hi = max(self.rows_hi, seq.row + 1)
             if not self._admit_ext(seq):
                 self._release(seq)  # no free slot of the penalty table: it waits, like for a row
                 break
-            if self.cfg.enable_prefix_caching:
+            # (mean pooling needs every token's hidden state: it matches no cached page)
+            if self.cfg.enable_prefix_caching and seq.params.embed != "mean":
                 self._match_prefix(seq)
                 if self._swa:  # a hit took all its pages: those below the window go straight back
                     self._release_window(seq, seq.num_cached)
@@ -1160,7 +1314,7 @@ class Engine:
             if not self._ensure_blocks(seq, seq.num_cached + n):
                 self._release(seq)  # matched prefix pages back to the cache, row freed
                 break
-            self.waiting.popleft()
+            del self.waiting[skip]
             # prefix-cache stats once per admission (a head request that waits for pages
             # re-matches every step and must not inflate the hit rate)
             self.stats["prefix_query_tokens"] += seq.length
@@ -1242,6 +1396,9 @@ class Engine:
                 return None
         p_ctx = [s.num_cached + n for s, n in zip(batch, chunks)]
         done = [c == s.length for s, c in zip(batch, p_ctx)]
+        # an embedding sequence's last chunk gets no logits row and joins nothing: emb_done, not done
+        emb_done = [d and s.params.embed is not None for s, d in zip(batch, done)]
+        done = [d and not e for d, e in zip(done, emb_done)]
         done_seqs = [s for s, d in zip(batch, done) if d]
         last = ids[rows]
         mctx = max(int(ctx_d.max()) if B else 0, max(p_ctx, default=0))
@@ -1296,6 +1453,8 @@ class Engine:
             if not st.greedy:
                 st.params = _ParamsList([s.params for s, q in zip(self.running, q_lens.tolist()) for _ in range(q)])
         st.batch, st.chunks, st.p_ctx, st.done, st.done_seqs = batch, chunks, p_ctx, done, done_seqs
+        st.emb_done, st.emb_out = emb_done, []
+        self._fill_pool(st)
         return st
 
     def _issue(self, st: _Step):
@@ -1368,6 +1527,8 @@ class Engine:
             out = self._decode_finish(st.rows, toks[:B], lp) if B else None
         if st.batch:
             p_out = self._chunks_done(st, [] if toks is None else toks[B:].tolist(), lp)
+            if st.emb_out:  # (the step has executed: the tokens were read, or the device synchronised)
+                p_out += self._deliver_embeds(st.emb_out)
             if out is None or p_out:
                 p_out = StepBatch.from_list(p_out)
                 out = p_out if out is None else StepBatch.concat(out, p_out)
@@ -1389,10 +1550,17 @@ class Engine:
         be); else those tokens (and ``lp``, the step's log-probabilities), applied at once: the
         StepOutputs are returned, and a sequence that ends with its first token never registers."""
         outs = []
-        for s, c, d, ti in zip(st.batch, st.p_ctx, st.done, itertools.accumulate(st.done, initial=st.B)):
+        for s, c, d, e, ti in zip(st.batch, st.p_ctx, st.done, st.emb_done,
+                                  itertools.accumulate(st.done, initial=st.B)):
             s.num_cached = c
             if self.cfg.enable_prefix_caching:
                 self._register_prefix(s, c)
+            if e:
+                # an embedding's last chunk is launched: its pages (the registered ones stay cached) and
+                # its row go back now, its slot when the vector is delivered (_deliver_embeds)
+                self.prefilling.remove(s)
+                st.emb_out.append((s, s.emb_slot, s.params.embed_dim or self.model.cfg.hidden_size))
+                self._release(s)
             if not d:
                 continue
             self.prefilling.remove(s)
@@ -1429,6 +1597,8 @@ class Engine:
         p = self._pending
         if p is None:
             return False
+        if any(s.status != Status.FINISHED for s, _, _ in p.emb):
+            return True
         return bool(len(p.rows)) and bool((self.r_epoch[p.rows] == p.epochs).any())
 
     def _record_meta_ev(self):
@@ -1513,7 +1683,7 @@ class Engine:
         self.r_tokidx[rows] = np.arange(B)
         self._chunks_done(st)
         pend = _Pending(st.srows, self.r_epoch[st.srows].copy(), seqs_d + st.done_seqs, toks_d, toks_h, ev,
-                        None if lp_h is None else (lp_h[0], lp_h[1], self.r_want[st.srows].copy()))
+                        None if lp_h is None else (lp_h[0], lp_h[1], self.r_want[st.srows].copy()), st.emb_out)
         self._retire_by_length(pend)
         self.stats["async_host_us"] += int(1e6 * (time.perf_counter() - t0))
         return pend
@@ -1552,7 +1722,16 @@ class Engine:
         return fin_stop
 
     def _async_post(self, pend) -> StepBatch:
-        """Apply an in-flight step's tokens (waits for that step only)."""
+        """Apply an in-flight step's tokens and deliver the embeddings it finished (waits for that
+        step only: both came back behind its own event)."""
+        out = self._async_post_tokens(pend)
+        if pend.emb:
+            e_out = self._deliver_embeds(pend.emb)
+            if e_out:
+                out = StepBatch.concat(out, StepBatch.from_list(e_out))
+        return out
+
+    def _async_post_tokens(self, pend) -> StepBatch:
         t0 = time.perf_counter()
         if pend.ev is not None:
             pend.ev.synchronize()
@@ -1635,6 +1814,14 @@ class Engine:
                 s = self.running[i]
                 # the row's length (async: it counts the in-flight step's token, s.length not yet)
                 if not self._ensure_blocks(s, int(ctx[i])):
+                    # an embedding sequence still in prefill is newer work than any running row: it
+                    # restarts from token 0 (its next first chunk overwrites its slot) before a row does
+                    victim = next((v for v in reversed(self.prefilling) if v.params.embed is not None), None)
+                    if victim is not None:
+                        self.prefilling.remove(victim)
+                        self._preempt(victim)
+                        ok = False
+                        break
                     self._preempt(self.running.pop())  # newest goes back to the queue
                     self._rows = self._rows[:-1]
                     self._outs.pop()
@@ -1799,6 +1986,8 @@ class Engine:
         self.meta.upload(T, nl, self.rows_hi)
         if self._step_lora:  # ahead of _meta_ev: the same event guards the pinned host side
             self._ts_d[:T].copy_(self._ts_h[:T], non_blocking=True)
+        if self._step_pool is not None:  # the pool segments and finish rows, under the same event
+            self._pool_d.copy_(self._pool_h, non_blocking=True)
         g = self._ids_gather
         if g is not None:
             # async: decode rows' input ids = the previous (in-flight) step's sampled tokens,
@@ -1855,6 +2044,8 @@ class Engine:
             hidden = self.model.forward(self.meta.ids_d[:T], meta, self.kv, lora=self.lora.step(self._ts_d[:T]))
         else:
             hidden = self.model.forward(self.meta.ids_d[:T], meta, self.kv)
+        if self._step_pool is not None:  # embedding chunks: pooled before the LM head (and when nl == 0)
+            self._pool_run(hidden)
         if nl == 0:
             return None
         return self._gather(self.model.logits_local(hidden[meta.logits_idx]), greedy)

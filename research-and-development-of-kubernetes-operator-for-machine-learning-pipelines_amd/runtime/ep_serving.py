@@ -115,6 +115,8 @@ def check_ep_request(params) -> None:
         raise ValueError("LoRA adapters are not supported by an expert-parallel (--ep) predictor")
     if params is not None and getattr(params, "guided", None) is not None:
         raise ValueError("guided decoding is not supported by an expert-parallel (--ep) predictor")
+    if params is not None and getattr(params, "embed", None) is not None:
+        raise ValueError("embedding requests are not supported by an expert-parallel (--ep) predictor")
 
 
 class EPGroupLoop:

@@ -94,6 +94,11 @@ class RuntimeMetrics:
         self.spec_accepted = Counter("mlop_spec_accepted_tokens", "Draft tokens accepted by speculative steps", base,
                                      registry=r)
         self._spec_seen = (0, 0)
+        # embedding requests served and their prompt tokens (exposed as ..._total); their HTTP requests
+        # count in the seldon_api_executor_* series under service="predictions" like infer
+        self.embed_requests = Counter("mlop_embedding_requests", "Embedding requests served", base, registry=r)
+        self.embed_tokens = Counter("mlop_embedding_tokens", "Prompt tokens of the embedding requests served", base,
+                                    registry=r)
         # the engine thread's perf_counter at the end of its last step AND the token total at that
         # instant, exported from ONE snapshot (``mark_step``): a rate over two scrapes then needs
         # no client-side clock (the scrape's own latency on a busy event loop skewed a 2-3 s
@@ -112,6 +117,11 @@ class RuntimeMetrics:
             self.engine_tokens.labels(**self.labels).inc(tokens)
         self._tok_total += tokens
         self._clock.snap = (self._tok_total, now)  # one reference store: scrapes see a consistent pair
+
+    def mark_embedding(self, tokens: int) -> None:
+        """Engine thread: one embedding request delivered its vector."""
+        self.embed_requests.labels(**self.labels).inc()
+        self.embed_tokens.labels(**self.labels).inc(tokens)
 
     def mark_spec(self, drafted: int, accepted: int) -> None:
         """Engine thread: the engine's running totals (Engine.stats) -> the two counters."""

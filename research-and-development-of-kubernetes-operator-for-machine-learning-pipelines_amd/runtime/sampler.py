@@ -29,6 +29,7 @@ I32_MAX = 2**31 - 1
 # slot, ep_serving.py) accepts and rejects the same requests
 MAX_STOP_IDS = 256
 MAX_LOGPROBS = 20  # top-N alternatives per token (sampling_ext.hip kLpMax)
+POOLING_MODES = ("last", "mean")  # SamplingParams.embed (pool.hip)
 
 
 @dataclass
@@ -48,6 +49,12 @@ class SamplingParams:
     # guided decoding (runtime/guided.py): exactly one of {"choice": [str, ...]}, {"regex": str},
     # {"json_schema": dict | str}; the output then fully matches it (engines with grammar_states > 0)
     guided: dict | None = None
+    # embedding request (engines with embed_slots > 0): no token is generated; the prompt's final-normed
+    # hidden states are pooled ("last": the last token's, "mean": over every token), cut to the first
+    # ``embed_dim`` components (None: all) and, under ``embed_normalize``, scaled to unit L2 norm
+    embed: str | None = None
+    embed_normalize: bool = True
+    embed_dim: int | None = None
 
     @property
     def greedy(self) -> bool:
@@ -102,6 +109,22 @@ class SamplingParams:
             from .guided import check_spec
 
             check_spec(self.guided)  # the shape only: Engine.check_request compiles it
+        if self.embed is None:
+            if self.embed_dim is not None or self.embed_normalize is not True:
+                raise ValueError("embed_dim / embed_normalize need embed (a pooling mode)")
+            return self
+        if self.embed not in POOLING_MODES:
+            raise ValueError(f"unknown pooling {self.embed!r} (supported: {', '.join(POOLING_MODES)}; CLS and other "
+                             "pooling modes of bidirectional encoders are not served)")
+        if not isinstance(self.embed_normalize, bool):
+            raise ValueError(f"embed_normalize must be a bool, got {self.embed_normalize!r}")
+        d = self.embed_dim
+        if d is not None and (isinstance(d, bool) or not isinstance(d, int) or not 1 <= d <= I32_MAX):
+            raise ValueError(f"embed_dim must be None or an int >= 1, got {d!r}")
+        for bad, what in ((self.guided is not None, "guided"), (self.logprobs is not None, "logprobs"),
+                          (self.penalised, "a penalty"), (self.adapter is not None, "adapter")):
+            if bad:
+                raise ValueError(f"an embedding request cannot carry {what}: it generates no token")
         return self
 
 

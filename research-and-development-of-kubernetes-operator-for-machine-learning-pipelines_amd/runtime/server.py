@@ -154,7 +154,22 @@ def _params(p: dict) -> SamplingParams:
             if not isinstance(v, dict):
                 raise ValueError("guided_json must be a JSON schema object (or its JSON text)")
             guided = {"json_schema": v}
-    return SamplingParams(adapter=ad, guided=guided,max_tokens=int(p.get("max_tokens", 64)), temperature=float(p.get("temperature", 0.0)),
+    pooling = p.get("pooling")
+    if pooling is not None and not isinstance(pooling, str):
+        raise ValueError(f"pooling must be a string, got {pooling!r}")
+    if pooling is None and (p.get("normalize") is not None or p.get("dimensions") is not None):
+        raise ValueError("normalize / dimensions need pooling (an embedding request)")
+    emb = {}
+    if pooling is not None:
+        norm, dim = p.get("normalize", True), p.get("dimensions")
+        if not isinstance(norm, bool):
+            raise ValueError(f"normalize must be a bool, got {norm!r}")
+        if dim is not None and (isinstance(dim, bool) or not isinstance(dim, int)):
+            raise ValueError(f"dimensions must be an int, got {dim!r}")
+        if p.get("encoding_format") not in (None, "float"):
+            raise ValueError("only float (JSON number) embeddings are served: no base64 / fp16 encodings")
+        emb = {"embed": pooling, "embed_normalize": norm, "embed_dim": dim}
+    return SamplingParams(**emb, adapter=ad, guided=guided,max_tokens=int(p.get("max_tokens", 64)), temperature=float(p.get("temperature", 0.0)),
                           top_k=int(p.get("top_k", 0)), top_p=float(p.get("top_p", 1.0)),
                           ignore_eos=bool(p.get("ignore_eos", False)),
                           stop_token_ids=list(p.get("stop_token_ids", [])),
@@ -223,6 +238,15 @@ def make_app(backend, metrics, version: str = "1", inject_latency_s: float | Non
             check(params)
         return params
 
+    def gen_params(p: dict) -> SamplingParams:
+        """``req_params`` of a request that generates tokens: embedding parameters are refused (400),
+        they belong to /embed or to infer's embedding form."""
+        params = req_params(p)
+        if params.embed is not None:
+            raise ValueError("parameters.pooling asks for an embedding: use POST /v2/models/{m}/embed or infer, "
+                             "not a generation endpoint")
+        return params
+
     async def live(_):
         return web.json_response({"live": True})
 
@@ -253,7 +277,20 @@ def make_app(backend, metrics, version: str = "1", inject_latency_s: float | Non
             return web.json_response({"model_name": backend.name, "model_version": version,
                                       "id": body.get("id", ""), "outputs": [
                                           {"name": "predict", "shape": list(y.shape), "datatype": dt, "data": data}]})
-        params = req_params(body.get("parameters", {}))
+        if (body.get("parameters") or {}).get("pooling") is not None or getattr(backend, "embedding_only", False):
+            # an embedding request: n strings, or one input_ids tensor -> one FP32 [n, d] tensor
+            params = embed_params(body.get("parameters"))
+            if "input_ids" in inputs:
+                prompts = [[int(v) for v in inputs["input_ids"]["data"]]]
+            else:
+                prompts = [backend.tokenizer.encode(str(t)) for t in inputs["text_input"]["data"]]
+            res, d, n = await run_embed(prompts, params)
+            data = [float(x) for r in res for x in r["embedding"]]
+            return web.json_response({"model_name": backend.name, "model_version": version, "id": body.get("id", ""),
+                                      "outputs": [{"name": "embedding", "shape": [len(res), d], "datatype": "FP32",
+                                                   "data": data}],
+                                      "parameters": {"prompt_tokens": n}})
+        params = gen_params(body.get("parameters", {}))
         if "input_ids" in inputs:
             ids = [int(v) for v in inputs["input_ids"]["data"]]
             res = await backend.generate(ids, params)
@@ -270,11 +307,62 @@ def make_app(backend, metrics, version: str = "1", inject_latency_s: float | Non
         return web.json_response({"model_name": backend.name, "model_version": version, "id": body.get("id", ""),
                                   "outputs": outs, "parameters": {"finish_reason": res["finish_reason"]}})
 
+    def embed_params(p: dict) -> SamplingParams:
+        """An embedding request's parameters: pooling / normalize default to the checkpoint's own
+        settings (sentence-transformers files; last, normalised without them)."""
+        p = dict(p or {})
+        pooling, normalize = backend.embedding_defaults() if hasattr(backend, "embedding_defaults") else (None, True)
+        if p.get("pooling") is None:
+            if pooling is None:
+                raise ValueError("this checkpoint names no pooling mode this runtime serves: the request must set "
+                                 "parameters.pooling (last | mean)")
+            p["pooling"] = pooling
+        if p.get("normalize") is None:  # (whether or not the request names its pooling)
+            p["normalize"] = normalize
+        return req_params(p)
+
+    async def run_embed(prompts, params):
+        """-> (results, d, prompt tokens); every input is checked before any is queued (400, none runs)."""
+        if not prompts:
+            raise ValueError("no input to embed")
+        check = getattr(getattr(backend, "engine", None), "check_request", None)
+        for ids in prompts:
+            if check is not None:
+                check(ids, params)  # empty / longer than max_model_len (never truncated) / ids outside the vocabulary
+        res = await backend.embed(prompts, params)
+        return res, int(res[0]["embedding"].shape[0]), sum(r["prompt_tokens"] for r in res)
+
+    def id_lists(v) -> list:
+        if not isinstance(v, list) or not v:
+            raise ValueError("input_ids must be a non-empty list of ints or of such lists")
+        rows = v if isinstance(v[0], list) else [v]
+        if any(not isinstance(r, list) or any(isinstance(t, bool) or not isinstance(t, int) for t in r) for r in rows):
+            raise ValueError("input_ids must be a non-empty list of ints or of such lists")
+        return rows
+
+    async def embed(req):
+        if backend.kind != "llm":
+            raise web.HTTPBadRequest(text="embed is only served by LLM predictors")
+        body = await req.json()
+        params = embed_params(body.get("parameters"))
+        if "input_ids" in body:
+            prompts = id_lists(body["input_ids"])
+        else:
+            texts = body.get("text_input")
+            texts = [texts] if isinstance(texts, str) else texts
+            if not isinstance(texts, list) or not texts or any(not isinstance(t, str) for t in texts):
+                raise ValueError("text_input must be a string or a non-empty list of strings")
+            prompts = [backend.tokenizer.encode(t) for t in texts]
+        res, d, n = await run_embed(prompts, params)
+        return web.json_response({"model_name": backend.name, "model_version": version,
+                                  "embeddings": [r["embedding"].tolist() for r in res], "dimensions": d,
+                                  "usage": {"prompt_tokens": n}})
+
     async def generate(req):
         if backend.kind != "llm":
             raise web.HTTPBadRequest(text="generate is only served by LLM predictors")
         body = await req.json()
-        params = req_params(body.get("parameters", body))
+        params = gen_params(body.get("parameters", body))
         ids = body["input_ids"] if "input_ids" in body else backend.tokenizer.encode(body.get("text_input", ""))
         res = await backend.generate(ids, params)
         out = {"model_name": backend.name, "model_version": version,
@@ -290,7 +378,7 @@ def make_app(backend, metrics, version: str = "1", inject_latency_s: float | Non
         if backend.kind != "llm":
             raise web.HTTPBadRequest(text="generate_stream is only served by LLM predictors")
         body = await req.json()
-        params = req_params(body.get("parameters", body))
+        params = gen_params(body.get("parameters", body))
         ids = body["input_ids"] if "input_ids" in body else backend.tokenizer.encode(body.get("text_input", ""))
         r = backend.submit(ids, params, stream=True)
         resp = web.StreamResponse(headers={"Content-Type": "text/event-stream"})
@@ -345,6 +433,7 @@ def make_app(backend, metrics, version: str = "1", inject_latency_s: float | Non
     r.add_get("/v2/models/{m}/ready", ready)
     r.add_post("/v2/models/{m}/infer", infer)
     r.add_post("/v2/models/{m}/generate", generate)
+    r.add_post("/v2/models/{m}/embed", embed)
     r.add_post("/v2/models/{m}/generate_stream", generate_stream)
     r.add_post("/api/v1.0/feedback", feedback)
     r.add_post("/api/v1.0/predictions", infer)
