@@ -255,11 +255,18 @@ def moe_combine(y, inv, topw):
 
 # ----------------------------------------------------------------- LoRA --
 
+def _lora_slots(tok_slot, S):
+    """int64 slots with every entry outside [0, S) turned into -1 (lora.hip lora_lane_slot)."""
+    ts = tok_slot.long()
+    return torch.where((ts < 0) | (ts >= S), torch.full_like(ts, -1), ts)
+
+
 def lora_shrink(x, A, tok_slot, slot_rank=None):
-    """tmp[t] = A[tok_slot[t]] . x[t] in fp32 ([T, G R]); rows with slot -1 are zero."""
+    """tmp[t] = A[tok_slot[t]] . x[t] in fp32 ([T, G R]); rows with slot -1, or with a slot outside
+    the storage (never an index), are zero."""
     T = x.shape[0]
     tmp = torch.zeros(T, A.shape[1], dtype=torch.float32, device=x.device)
-    ts = tok_slot.long()
+    ts = _lora_slots(tok_slot, A.shape[0])
     for s in torch.unique(ts[ts >= 0]).tolist():
         rows = ts == s
         tmp[rows] = x[rows].float() @ A[s].float().t()
@@ -268,9 +275,10 @@ def lora_shrink(x, A, tok_slot, slot_rank=None):
 
 def lora_expand_add(y, tmp, B, tile_group, tok_slot, slot_rank=None):
     """In place: y[t, n] += sum_r tmp[t, g(n) R + r] . B[tok_slot[t], n, r] (fp32 sum, one rounding to
-    y's dtype); g(n) = tile_group[n // 16].  Rows with slot -1 are not written."""
+    y's dtype); g(n) = tile_group[n // 16].  Rows with slot -1, or with a slot outside the storage,
+    are not written."""
     R = B.shape[2]
-    ts = tok_slot.long()
+    ts = _lora_slots(tok_slot, B.shape[0])
     col_g = tile_group.long().repeat_interleave(16)
     for s in torch.unique(ts[ts >= 0]).tolist():
         rows = torch.nonzero(ts == s, as_tuple=True)[0]
