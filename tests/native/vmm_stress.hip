@@ -18,6 +18,7 @@
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
+#include <string>
 #include <thread>
 #include <vector>
 
@@ -64,7 +65,19 @@ static void poll_until(void* base, long target, int threads) {
   CHECK(!fail.load());
 }
 
-int main() {
+int main(int argc, char** argv) {
+  // --probe: only report whether this build can open the GPU at all (exit 0) or not (exit 3).
+  // ThreadSanitizer's fixed x86-64 layout keeps 16 TiB - 85 TiB of the address space for
+  // its shadow and the protected gap behind it; a driver that hands out GPU-visible address
+  // space only inside that window (seen with virtualised GPUs) leaves a TSan process without
+  // a device, whatever the code under test.  tests/test_native_sanitizers_gpu.py compares
+  // this probe of the TSan build with the plain build's.
+  if (argc > 1 && std::string(argv[1]) == "--probe") {
+    int n = 0;
+    const hipError_t e = hipGetDeviceCount(&n);
+    std::printf("probe: %d device(s), %s\n", n, hipGetErrorString(e));
+    return e == hipSuccess && n > 0 ? 0 : 3;
+  }
   int dev = 0;
   CHECK(hipSetDevice(dev) == hipSuccess);
   if (!vmm_supported(dev)) {
