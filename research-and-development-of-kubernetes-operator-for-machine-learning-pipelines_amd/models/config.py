@@ -35,6 +35,8 @@ class ModelConfig:
     # MoE (Mixtral): 0 experts = dense MLP
     num_experts: int = 0
     top_k: int = 2
+    # the top-k router weights are divided by their sum (Mixtral always; Qwen3-MoE's norm_topk_prob)
+    norm_topk_prob: bool = True
     rope_scaling: dict | None = field(default=None, hash=False, compare=False)
     eos_token_id: int = 128001
     # further end-of-sequence ids (HF eos_token_id lists, e.g. Llama-3.1-Instruct's
@@ -165,6 +167,14 @@ PRESETS = {c.name: c for c in (LLAMA3_8B, LLAMA3_70B, LLAMA31_8B, LLAMA31_70B, M
 # entry there would change that yardstick.  get_config, ALIASES and loader.known_preset look here
 # too; the routes of these shapes are pinned in a fixture of their own.
 CHECKPOINT_SHAPES = {c.name: c for c in (QWEN3_8B, QWEN3_32B)}
+# Qwen3-30B-A3B: public HF config.json of Qwen/Qwen3-30B-A3B (128 experts, top-8, 3 B active; the
+# Mixtral model class with QK-norm attention and the wide route).  A dict of its own: PRESETS and
+# CHECKPOINT_SHAPES both feed pinned planner fixtures that this shape must not change.
+QWEN3_30B_A3B = ModelConfig(
+    name="qwen3-30b-a3b", vocab_size=151936, hidden_size=2048, intermediate_size=768, num_layers=48,
+    num_heads=32, num_kv_heads=4, rope_theta=1e6, rms_eps=1e-6, max_position=40960, eos_token_id=151645,
+    num_experts=128, top_k=8, norm_topk_prob=True, qk_norm=True)
+MOE_CHECKPOINT_SHAPES = {c.name: c for c in (QWEN3_30B_A3B,)}
 # accepted aliases (MLflow tags / CR annotations use HF-ish names)
 ALIASES = {
     "meta-llama/Meta-Llama-3-8B": "llama3-8b", "llama-3-8b": "llama3-8b", "Llama-3-8B": "llama3-8b",
@@ -174,12 +184,13 @@ ALIASES = {
     "mistralai/Mixtral-8x7B-v0.1": "mixtral-8x7b", "Mixtral-8x7B": "mixtral-8x7b",
     "mistralai/Mistral-7B-v0.1": "mistral-7b", "Mistral-7B": "mistral-7b",
     "Qwen/Qwen3-8B": "qwen3-8b", "Qwen3-8B": "qwen3-8b", "Qwen/Qwen3-32B": "qwen3-32b", "Qwen3-32B": "qwen3-32b",
+    "Qwen/Qwen3-30B-A3B": "qwen3-30b-a3b", "Qwen3-30B-A3B": "qwen3-30b-a3b",
 }
 
 
 def get_config(name: str, **overrides) -> ModelConfig:
     key = ALIASES.get(name, name)
-    cfg = PRESETS.get(key) or CHECKPOINT_SHAPES.get(key)
+    cfg = PRESETS.get(key) or CHECKPOINT_SHAPES.get(key) or MOE_CHECKPOINT_SHAPES.get(key)
     if cfg is None:
-        raise KeyError(f"unknown model '{name}' (known: {sorted([*PRESETS, *CHECKPOINT_SHAPES])})")
+        raise KeyError(f"unknown model '{name}' (known: {sorted([*PRESETS, *CHECKPOINT_SHAPES, *MOE_CHECKPOINT_SHAPES])})")
     return replace(cfg, **overrides) if overrides else cfg

@@ -3,7 +3,7 @@
 The operator hands a predictor its MLflow artifact URI (``s3://mlflow/<rel>``, reference
 ``mlflow_operator.py:125-127``).  When that artifact is reachable as a local directory
 (``file://`` URI, a plain path, or ``s3://mlflow/<rel>`` under ``MLOP_ARTIFACT_ROOT``)
-holding a Llama / Mistral / Mixtral / Qwen3 (dense) checkpoint in the HF layout, the runtime serves those weights;
+holding a Llama / Mistral / Mixtral / Qwen3 (dense or MoE) checkpoint in the HF layout, the runtime serves those weights;
 otherwise it random-initialises the architecture named by the CR / MLflow tags (the
 benchmark configuration: no checkpoints are downloadable here).
 
@@ -19,6 +19,8 @@ Layout mapping (HF name -> ours; TP sharding then reuses ``load_shard_from``):
   Mixtral: block_sparse_moe.gate | mlp.gate      -> router
            experts.{e}.w1 / w3 (legacy) or experts.gate_up_proj (fused) -> w13 (interleaved)
            experts.{e}.w2 or experts.down_proj   -> w2
+  Qwen3-MoE: mlp.gate -> router; experts.{e}.{gate,up}_proj (hub checkpoints) or experts.gate_up_proj -> w13;
+           experts.{e}.down_proj or experts.down_proj -> w2
 Tensors are read lazily, one layer at a time (safetensors memory map), so a 141 GB
 checkpoint never sits in host memory at once.
 """
@@ -31,11 +33,14 @@ from pathlib import Path
 
 import torch
 
-from .config import CHECKPOINT_SHAPES, ModelConfig, PRESETS
+from .config import CHECKPOINT_SHAPES, MOE_CHECKPOINT_SHAPES, ModelConfig, PRESETS
 
-# Qwen3 (dense) is the Llama layer with a per-head QK-norm before RoPE (ModelConfig.qk_norm)
+# Qwen3 (dense) is the Llama layer with a per-head QK-norm before RoPE (ModelConfig.qk_norm);
+# Qwen3-MoE is the Mixtral block on that layer, routed over 128 experts (ops.moe_dispatch_wide)
 _ARCH_NAMES = {"LlamaForCausalLM": "llama", "MixtralForCausalLM": "mixtral", "MistralForCausalLM": "llama",
-               "Qwen3ForCausalLM": "llama"}
+               "Qwen3ForCausalLM": "llama", "Qwen3MoeForCausalLM": "mixtral"}
+# keys a Qwen3-MoE config.json must name itself (transformers' defaults are never filled in)
+_QWEN3_MOE_KEYS = ("moe_intermediate_size", "num_experts_per_tok", "norm_topk_prob")
 # base-model checkpoints (decoder-style embedding models): the same layers, tensor names without the
 # "model." prefix, no lm_head.weight; they serve embedding requests only (ModelConfig.embedding_only)
 _BASE_ARCHS = {"LlamaModel": "LlamaForCausalLM", "MistralModel": "MistralForCausalLM", "Qwen3Model": "Qwen3ForCausalLM"}
@@ -83,9 +88,23 @@ def config_from_hf(d: dict, name: str | None = None) -> ModelConfig:
     arch = (d.get("architectures") or ["LlamaForCausalLM"])[0]
     embedding_only = arch in _BASE_ARCHS
     arch = _BASE_ARCHS.get(arch, arch)
-    if arch == "Qwen3MoeForCausalLM":
-        raise ValueError("Qwen3-MoE checkpoints are not supported: their router (norm_topk_prob, 128 experts) "
-                         "differs from Mixtral's; only the dense Qwen3ForCausalLM loads")
+    moe3 = arch == "Qwen3MoeForCausalLM"
+    if moe3:
+        # a config that leaves one of these out would be served on transformers' defaults: a silent
+        # guess.  (tests/test_qwen3_cpu.py test_rejected_configs feeds a dense Qwen3 config under this
+        # architecture name, with none of the three MoE keys: it is refused here, naming Qwen3-MoE)
+        for key in _QWEN3_MOE_KEYS:
+            if d.get(key) is None:
+                raise ValueError(f"Qwen3-MoE config.json does not name {key!r} (required: {', '.join(_QWEN3_MOE_KEYS)})")
+        if d.get("mlp_only_layers"):
+            raise ValueError(f"Qwen3-MoE mlp_only_layers={d['mlp_only_layers']} is not supported (every layer is sparse)")
+        if int(d.get("decoder_sparse_step", 1)) != 1:
+            raise ValueError(f"Qwen3-MoE decoder_sparse_step={d['decoder_sparse_step']} is not supported (only 1)")
+        n_exp = d.get("num_experts", d.get("num_local_experts"))  # (transformers 5 writes the second name)
+        if n_exp != 128:
+            raise ValueError(f"Qwen3-MoE num_experts={n_exp} is not supported (the wide route takes 128)")
+        if int(d["num_experts_per_tok"]) > 8:
+            raise ValueError(f"Qwen3-MoE num_experts_per_tok={d['num_experts_per_tok']} is not supported (at most 8)")
     if arch not in _ARCH_NAMES:
         raise ValueError(f"unsupported checkpoint architecture {arch!r} (supported: {sorted(_ARCH_NAMES)}, and the "
                          f"base models {sorted(_BASE_ARCHS)} for embeddings; bidirectional encoders, rerankers and "
@@ -124,7 +143,7 @@ def config_from_hf(d: dict, name: str | None = None) -> ModelConfig:
         if d.get(flag):
             raise ValueError(f"{flag}=true is not supported (bias tensors are not loaded)")
     nkv = d.get("num_key_value_heads") or nh
-    qk_norm = arch == "Qwen3ForCausalLM"
+    qk_norm = arch == "Qwen3ForCausalLM" or moe3
     if qk_norm and (nh % nkv or nh // nkv not in _GQA_GROUPS):
         # (Qwen3-14B: 40 query heads over 8 KV heads) fail here, not in a device-path check
         raise ValueError(f"GQA group {nh}/{nkv} = {nh / nkv:g} is not supported: the attention kernels take "
@@ -134,12 +153,13 @@ def config_from_hf(d: dict, name: str | None = None) -> ModelConfig:
     eos = eos_all[0]
     return ModelConfig(
         name=name or d.get("_name_or_path") or arch, vocab_size=d["vocab_size"], hidden_size=H,
-        intermediate_size=d["intermediate_size"], num_layers=d["num_hidden_layers"], num_heads=nh,
+        intermediate_size=d["moe_intermediate_size"] if moe3 else d["intermediate_size"], num_layers=d["num_hidden_layers"], num_heads=nh,
         num_kv_heads=nkv, head_dim=d.get("head_dim") or H // nh,
         rope_theta=float(theta), rms_eps=float(d.get("rms_norm_eps", 1e-5)),
         max_position=max_pos,
         tie_embeddings=bool(d.get("tie_word_embeddings", False)) or embedding_only, embedding_only=embedding_only,
-        num_experts=int(d.get("num_local_experts", 0) or 0), top_k=int(d.get("num_experts_per_tok", 2)),
+        num_experts=128 if moe3 else int(d.get("num_local_experts", 0) or 0),
+        top_k=int(d.get("num_experts_per_tok", 2)), norm_topk_prob=bool(d["norm_topk_prob"]) if moe3 else True,
         rope_scaling=scaling, eos_token_id=int(eos), extra_eos_ids=eos_all[1:], sliding_window=window,
         qk_norm=qk_norm)
 
@@ -214,6 +234,13 @@ class HFWeights:
                                                                    t.get(m + f"experts.{e}.w3.weight"))
                                                 for e in range(E)])
                 L["w2"] = lambda: torch.stack([t.get(m + f"experts.{e}.w2.weight") for e in range(E)])
+            elif t.has(p + "mlp.experts.0.gate_proj.weight"):  # Qwen3-MoE per-expert layout (hub checkpoints)
+                m = p + "mlp."
+                L["router"] = lambda: t.get(m + "gate.weight")
+                L["w13"] = lambda: torch.stack([interleave_gate_up(t.get(m + f"experts.{e}.gate_proj.weight"),
+                                                                   t.get(m + f"experts.{e}.up_proj.weight"))
+                                                for e in range(E)])
+                L["w2"] = lambda: torch.stack([t.get(m + f"experts.{e}.down_proj.weight") for e in range(E)])
             else:  # fused expert tensors (transformers >= 5 module layout)
                 m = p + "mlp."
                 L["router"] = lambda: t.get(m + "gate.weight")
@@ -272,7 +299,7 @@ def load_pretrained(path: str | os.PathLike, device="cuda", dtype=torch.bfloat16
 
 def known_preset(cfg: ModelConfig) -> str | None:
     """Name of the preset with the same shapes (placement / reporting), if any."""
-    for n, p in (*PRESETS.items(), *CHECKPOINT_SHAPES.items()):
+    for n, p in (*PRESETS.items(), *CHECKPOINT_SHAPES.items(), *MOE_CHECKPOINT_SHAPES.items()):
         if replace(p, name=cfg.name, eos_token_id=cfg.eos_token_id, rope_scaling=cfg.rope_scaling,
                    max_position=cfg.max_position) == cfg:
             return n

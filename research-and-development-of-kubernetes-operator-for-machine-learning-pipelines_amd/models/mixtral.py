@@ -24,6 +24,12 @@ class MixtralModel(LlamaModel):
         E, H, I = cfg.num_experts, cfg.hidden_size, cfg.intermediate_size
         ep = self.ps.ep.size
         assert E % ep == 0, "experts must divide by EP size"
+        if E > 64 and (ep > 1 or self.ps.tp_size > 1):
+            # the wide route (ops.moe_dispatch_wide) serves one rank; sharding it is not built
+            raise ValueError(f"{cfg.name}: a model with more than 64 experts ({E}) is served on one GPU only "
+                             f"(TP = {self.ps.tp_size}, EP = {ep} asked)")
+        if E <= 64 and not cfg.norm_topk_prob:
+            raise ValueError(f"{cfg.name}: norm_topk_prob = false needs the wide route (more than 64 experts)")
         self.n_local_experts = E // ep
         self.expert_start = self.ps.ep.rank * self.n_local_experts
         return {
@@ -55,7 +61,7 @@ class MixtralModel(LlamaModel):
         cap = getattr(self, "moe_capacity_tokens", None)
         return moe_forward(x, L["router"], L["w13"], L["w2"], self.cfg.top_k, self.ps.ep,
                            self.expert_start, self.n_local_experts, mode=mode,
-                           cap_tokens=max(cap or 0, x.shape[0]))
+                           cap_tokens=max(cap or 0, x.shape[0]), renorm=self.cfg.norm_topk_prob)
 
     def mlp_row_parallel(self, i, x, residual, next_norm, eps):
         """TP > 1 (experts sharded over the TP ranks): each rank's partial MoE output, summed by
@@ -72,19 +78,22 @@ class MixtralModel(LlamaModel):
 
             L = self.layers[i]
             return moe_forward_add_norm(x, L["router"], L["w13"], L["w2"], self.cfg.top_k, self.expert_start,
-                                        self.n_local_experts, residual, next_norm, eps)
+                                        self.n_local_experts, residual, next_norm, eps,
+                                        renorm=self.cfg.norm_topk_prob)
         return ops.add_rmsnorm(self.mlp(i, x), residual, next_norm, eps)
 
     def attn_out_mlp(self, i, a, residual, next_norm, eps):
         """TP = EP = 1 decode sizes: O projection GEMV, then ONE launch for residual add +
         post-attention RMSNorm + router + route + sort + gather (moe_dispatch_small's
-        prologue), the two grouped GEMMs, and the combine fused into the next add + norm."""
+        prologue), the two grouped GEMMs, and the combine fused into the next add + norm.
+        More than 64 experts: the add + norm is a launch of its own before the wide dispatch."""
         if self.ps.ep.size == 1 and a.is_cuda and a.shape[0] <= 16:
             from ..parallel.moe import moe_forward_add_norm
 
             L = self.layers[i]
             o = linear(a, L["o"])
             return moe_forward_add_norm(None, L["router"], L["w13"], L["w2"], self.cfg.top_k, self.expert_start,
-                                        self.n_local_experts, residual, next_norm, eps, pre=(o, L["post_norm"]))
+                                        self.n_local_experts, residual, next_norm, eps, pre=(o, L["post_norm"]),
+                                        renorm=self.cfg.norm_topk_prob)
         return super().attn_out_mlp(i, a, residual, next_norm, eps)
 

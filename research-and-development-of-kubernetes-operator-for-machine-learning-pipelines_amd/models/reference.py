@@ -18,7 +18,8 @@ def _mlp(model, i, x):
     if model.cfg.is_moe:
         logits = F.linear(x, L["router"].float())
         w, idx = torch.topk(torch.softmax(logits, -1), model.cfg.top_k, dim=-1)
-        w = w / w.sum(-1, keepdim=True)
+        if model.cfg.norm_topk_prob:
+            w = w / w.sum(-1, keepdim=True)
         out = torch.zeros_like(x)
         for e in range(model.cfg.num_experts):
             rows, k = (idx == e).nonzero(as_tuple=True)

@@ -1027,6 +1027,45 @@ def moe_dispatch_mid(x, router_w, top_k: int, e0: int, n_local: int, pro=None):
     return topw, topi, xs, offsets, arow, inv
 
 
+def moe_route_wide(x, router_w, top_k: int, renorm: bool = True):
+    """Route over 128 experts in ONE launch (moe_wide.hip): the router GEMM on the matrix cores,
+    bf16-rounded logits, softmax, top-k (ties to the lower id) and, with ``renorm``, the division
+    by the picked weights' sum.  x bf16 [T, H], router_w bf16 [128, H] -> (w f32 [T,k], idx int32 [T,k])."""
+    if not x.is_cuda:
+        return ref.moe_route(torch.nn.functional.linear(x, router_w), top_k, renorm)
+    _need_gpu()
+    T = x.shape[0]
+    topw = torch.empty(T, top_k, dtype=torch.float32, device=x.device)
+    topi = torch.empty(T, top_k, dtype=torch.int32, device=x.device)
+    torch.ops.mlop.moe_route_wide(topw, topi, x.contiguous(), router_w.contiguous(), bool(renorm))
+    return topw, topi
+
+
+def moe_dispatch_wide(x, router_w, top_k: int, e0: int, n_local: int, renorm: bool = True):
+    """MoE dispatch for 128 experts, 1 <= T <= 16384, in two stream-ordered launches
+    (moe_wide.hip): ``moe_route_wide``, then one workgroup that sorts the T*k slots by local
+    expert.  Returns moe_dispatch_mid's tuple (topw, topi, x, offsets, arow, inv): the grouped
+    GEMM reads x through arow, there is no gathered copy.  A shape the kernels do not take raises."""
+    if not x.is_cuda:
+        topw, topi = moe_route_wide(x, router_w, top_k, renorm)
+        _xp, offsets, src, inv = ref.moe_permute(x, topi, e0, n_local)
+        return topw, topi, x, offsets, torch.div(src, top_k, rounding_mode="floor"), inv
+    xs = x.contiguous()
+    topw, topi = moe_route_wide(xs, router_w, top_k, renorm)
+    n = topi.numel()
+    offsets = torch.empty(n_local + 1, dtype=torch.int32, device=x.device)
+    arow = torch.empty(n, dtype=torch.int32, device=x.device)
+    inv = torch.empty(n, dtype=torch.int32, device=x.device)
+    torch.ops.mlop.moe_place_wide(offsets, arow, inv, topi, e0, n_local)
+    return topw, topi, xs, offsets, arow, inv
+
+
+def moe_wide_takes(T: int, E: int, k: int, H: int) -> bool:
+    """Whether the wide dispatch's kernels take the shape (a pure host predicate of moe_wide.hip)."""
+    _need_gpu()
+    return bool(torch.ops.mlop.moe_wide_takes(T, E, k, H))
+
+
 def moe_combine_add_rmsnorm(y, inv, topw, residual, norm_w, eps: float):
     """residual <- residual + combine(y); returns rmsnorm(residual) * norm_w (one launch on GPU)."""
     if y.is_cuda:

@@ -751,6 +751,43 @@ bool moe_dispatch_mid(Tensor topw, Tensor topi, Tensor offsets, Tensor arow, Ten
   return true;
 }
 
+// wide dispatch (128 experts; moe_wide.hip), launch 1: router GEMM on the matrix cores + softmax + top-k
+void moe_route_wide(Tensor topw, Tensor topi, Tensor x, Tensor router_w, bool renorm) {
+  check_bf16(x, "x"); check_bf16(router_w, "router_w"); check_i32(topi, "topi");
+  TORCH_CHECK(x.dim() == 2 && x.is_contiguous() && router_w.dim() == 2 && router_w.is_contiguous() &&
+                  router_w.size(1) == x.size(1), "x [T, H], router_w [E, H], both contiguous");
+  const int64_t T = x.size(0), H = x.size(1), E = router_w.size(0);
+  TORCH_CHECK(topi.dim() == 2 && topi.is_contiguous() && topi.size(0) == T, "topi [T, k]");
+  const int64_t k = topi.size(1);
+  TORCH_CHECK(E == 128, "moe_route_wide: ", E, " experts (only 128 is instantiated)");
+  TORCH_CHECK(k >= 1 && k <= 8, "moe_route_wide: top_k ", k, " outside 1..8");
+  TORCH_CHECK(T <= 16384, "moe_route_wide: ", T, " tokens (at most 16384)");
+  TORCH_CHECK(H >= 128 && H % 32 == 0 && (T > 16 || H % 128 == 0), "moe_route_wide: hidden size ", H,
+              " (a multiple of 32 from 128 up; of 128 for T <= 16, the K-split form)");
+  TORCH_CHECK(topw.scalar_type() == at::kFloat && topw.is_contiguous() && topw.numel() == T * k, "topw f32 [T, k]");
+  TORCH_CHECK(T == 0 || mlop::moe_wide_takes((int)T, (int)E, (int)k, (int)H), "moe_route_wide: shape not taken");
+  c10::DeviceGuard g(x.device());
+  mlop::launch_moe_route_wide(topw.data_ptr<float>(), topi.data_ptr<int>(), x.data_ptr(), router_w.data_ptr(), (int)T,
+                              (int)E, (int)k, (int)H, renorm, cur_stream());
+}
+
+// wide dispatch, launch 2: offsets / inv / arow of the routed slots (one workgroup)
+void moe_place_wide(Tensor offsets, Tensor arow, Tensor inv, Tensor topi, int64_t e0, int64_t n_local) {
+  check_i32(offsets, "offsets"); check_i32(arow, "arow"); check_i32(inv, "inv"); check_i32(topi, "topi");
+  TORCH_CHECK(topi.dim() == 2 && topi.is_contiguous(), "topi [T, k]");
+  const int64_t T = topi.size(0), k = topi.size(1);
+  TORCH_CHECK(k >= 1 && T * k <= 131072, "moe_place_wide: ", T * k, " slots (at most 131072)");
+  TORCH_CHECK(n_local >= 1 && n_local <= 256 && offsets.numel() == n_local + 1 && arow.numel() == T * k &&
+                  inv.numel() == T * k, "offsets [n_local + 1 <= 257], arow / inv [T*k]");
+  c10::DeviceGuard g(topi.device());
+  mlop::launch_moe_place_wide(offsets.data_ptr<int>(), arow.data_ptr<int>(), inv.data_ptr<int>(),
+                              topi.data_ptr<int>(), (int)T, (int)k, (int)e0, (int)n_local, cur_stream());
+}
+
+bool moe_wide_takes(int64_t T, int64_t E, int64_t k, int64_t H) {
+  return mlop::moe_wide_takes((int)T, (int)E, (int)k, (int)H);
+}
+
 bool moe_combine_add_rmsnorm(Tensor out, Tensor residual, Tensor y, Tensor inv, Tensor topw, Tensor norm_w,
                              double eps) {
   check_bf16(out, "out"); check_bf16(residual, "residual"); check_bf16(y, "y"); check_bf16(norm_w, "norm_w");
@@ -1275,6 +1312,9 @@ TORCH_LIBRARY(mlop, m) {
   m.def("moe_dispatch_mid(Tensor(a!) topw, Tensor(b!) topi, Tensor(c!) offsets, Tensor(d!) arow, Tensor(e!) inv, "
         "Tensor(f!) x, Tensor router_w, int e0, int n_local, Tensor? pro_y=None, Tensor(g!)? pro_res=None, "
         "Tensor? pro_w=None, float pro_eps=0.0) -> bool");
+  m.def("moe_route_wide(Tensor(a!) topw, Tensor(b!) topi, Tensor x, Tensor router_w, bool renorm) -> ()");
+  m.def("moe_place_wide(Tensor(a!) offsets, Tensor(b!) arow, Tensor(c!) inv, Tensor topi, int e0, int n_local) -> ()");
+  m.def("moe_wide_takes(int T, int E, int k, int H) -> bool", &moe_wide_takes);
   m.def("moe_down_combine_add_rmsnorm(Tensor(a!) out, Tensor(b!) residual, Tensor(c!) y, Tensor a, Tensor w2, "
         "Tensor offsets, int max_rows, Tensor inv, Tensor topw, Tensor norm_w, float eps) -> bool");
   m.def("moe_combine_add_rmsnorm(Tensor(a!) out, Tensor(b!) residual, Tensor y, Tensor inv, Tensor topw, "
@@ -1350,6 +1390,8 @@ TORCH_LIBRARY_IMPL(mlop, CUDA, m) {
   m.impl("moe_route", &moe_route);
   m.impl("moe_dispatch_small", &moe_dispatch_small);
   m.impl("moe_dispatch_mid", &moe_dispatch_mid);
+  m.impl("moe_route_wide", &moe_route_wide);
+  m.impl("moe_place_wide", &moe_place_wide);
   m.impl("moe_down_combine_add_rmsnorm", &moe_down_combine_add_rmsnorm);
   m.impl("moe_combine_add_rmsnorm", &moe_combine_add_rmsnorm);
   m.impl("moe_permute", &moe_permute);

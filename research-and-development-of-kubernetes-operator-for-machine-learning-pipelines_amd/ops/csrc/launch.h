@@ -181,6 +181,14 @@ void launch_moe_dispatch_small(float* topw, int* topi, void* xp, int* offsets, i
 // combine + residual add + RMSNorm in one launch; false = hidden size not instantiated
 bool launch_moe_combine_add_rmsnorm(void* out, void* residual, const void* y, const int* inv, const float* topw,
                                     const void* w, float eps, int T, int k, int H, hipStream_t st);
+// wide MoE dispatch (128 experts, top-k <= 8; moe_wide.hip): two stream-ordered launches.
+// route: router GEMM on the matrix cores + softmax + top-k (+ renormalise) in registers -> topw, topi;
+// place: one workgroup sorts the T*k slots by local expert -> offsets, inv, arow (moe_dispatch_mid's meaning)
+bool moe_wide_takes(int T, int E, int k, int H);
+void launch_moe_route_wide(float* topw, int* topi, const void* x, const void* wr, int T, int E, int k, int H,
+                           bool renorm, hipStream_t st);
+void launch_moe_place_wide(int* offsets, int* arow, int* inv, const int* topi, int T, int k, int e0, int n_local,
+                           hipStream_t st);
 void launch_argmax(long* out, const float* logits, int n, int V, long ld, hipStream_t st);
 // bf16 greedy argmax; ws (>= argmax_splits(n, V) * n int64, or null) splits small batches' rows
 int argmax_splits(int n, int V);

@@ -23,8 +23,18 @@ from .. import ops
 from ..models.layers import linear
 
 
-def route(x: torch.Tensor, router_w: torch.Tensor, top_k: int):
-    """softmax(x @ Wr^T) -> top-k -> renormalised weights (Mixtral). fp32 [T,k], int32 [T,k]."""
+# more experts than the one-thread-per-token routes of moe.hip hold (64): the wide route of
+# moe_wide.hip (router GEMM on the matrix cores + top-k in one launch; Qwen3-MoE's 128 experts)
+WIDE_EXPERTS = 64
+
+
+def route(x: torch.Tensor, router_w: torch.Tensor, top_k: int, renorm: bool = True):
+    """softmax(x @ Wr^T) -> top-k -> renormalised weights (Mixtral). fp32 [T,k], int32 [T,k].
+    ``renorm=False``: the softmax weights of the picked experts as they are (wide route only)."""
+    if router_w.shape[0] > WIDE_EXPERTS:
+        return ops.moe_route_wide(x, router_w, top_k, renorm)
+    if not renorm:
+        raise ValueError("top-k weights that are not renormalised need the wide route (more than 64 experts)")
     logits = linear(x, router_w)
     return ops.moe_route(logits, top_k)
 
@@ -56,13 +66,23 @@ def local_experts(x, topw, topi, w13, w2, e0: int, n_local: int, dispatched=None
 
 
 def moe_forward_add_norm(x, router_w, w13, w2, top_k: int, e0: int, n_local: int, residual, norm_w, eps: float,
-                         pre=None):
+                         pre=None, renorm: bool = True):
     """Single-rank MoE block followed by the decoder's residual add + RMSNorm.  At decode
     sizes the router GEMV, routing, sort and gather are ONE launch (moe_dispatch_small; at
     16 < T <= 16384 moe_dispatch_mid, whose experts read x in place) and the weighted combine
     rides in the add + RMSNorm launch: 6 MoE glue launches -> 2.
     ``pre=(o, pre_norm_w)``: x is not formed yet; the block's own input add + RMSNorm
-    (residual += o, x = rmsnorm(residual)) becomes the dispatch launch's prologue."""
+    (residual += o, x = rmsnorm(residual)) becomes the dispatch launch's prologue.
+    More than 64 experts: the wide dispatch (two launches at every T, no fused prologue: the
+    input add + RMSNorm runs first), then the same expert GEMMs and fused tail."""
+    if router_w.shape[0] > WIDE_EXPERTS:
+        if pre is not None:
+            x = ops.add_rmsnorm(pre[0], residual, pre[1], eps)
+        topw, topi, xs, offsets, arow, inv = ops.moe_dispatch_wide(x, router_w, top_k, e0, n_local, renorm)
+        return local_experts(xs, topw, topi, w13, w2, e0, n_local, dispatched=(xs, offsets, inv, arow),
+                             combine=(residual, norm_w, eps))
+    if not renorm:
+        raise ValueError("top-k weights that are not renormalised need the wide route (more than 64 experts)")
     mid = None
     if pre is not None:
         o, pre_w = pre
@@ -89,8 +109,8 @@ def moe_forward_add_norm(x, router_w, w13, w2, top_k: int, e0: int, n_local: int
 
 
 def moe_forward(x, router_w, w13, w2, top_k: int, ep, e0: int, n_local: int, mode: str = "allreduce",
-                cap_tokens: int | None = None):
-    topw, topi = route(x, router_w, top_k)
+                cap_tokens: int | None = None, renorm: bool = True):
+    topw, topi = route(x, router_w, top_k, renorm)
     if ep.size == 1 or mode == "allreduce":
         return local_experts(x, topw, topi, w13, w2, e0, n_local)
     ex = getattr(ep, "ex", None)
