@@ -87,6 +87,7 @@ class CanaryPolicy:
 
 
 KV_CACHE_DTYPES = ("bf16", "fp8")  # spec.kvCacheDtype (manifests/crd.yaml's enum)
+WEIGHT_DTYPES = ("bf16", "int4")  # spec.weightDtype (manifests/crd.yaml's enum)
 MAX_SPECULATIVE_TOKENS = 7         # spec.speculativeTokens (manifests/crd.yaml's maximum; runtime/spec.py)
 MAX_GUIDED_STATES = 32767          # spec.guidedDecodingStates (int16 arena entries; runtime/guided.py)
 MAX_EMBEDDING_SLOTS = 4096         # spec.embeddingSlots (manifests/crd.yaml's maximum; EngineConfig.embed_slots)
@@ -111,6 +112,8 @@ class ModelSpec:
     adapters: tuple = ()
     # KV cache element type of the LLM runtime: None / "bf16", or "fp8" (e4m3fn pages + row scales)
     kv_cache_dtype: str | None = None
+    # projection weights of the LLM runtime: None / "bf16", or "int4" (group-128 symmetric, quantised at load)
+    weight_dtype: str | None = None
     # draft tokens per step of the LLM runtime's prompt-lookup speculative decoding: None / 0 = off, 1..7
     speculative_tokens: int | None = None
     # rows of the LLM runtime's guided-decoding grammar arena: None / 0 = off, up to 32767
@@ -134,6 +137,7 @@ class ModelSpec:
                    adapters=tuple((a.get("name"), a.get("uri")) for a in (spec.get("adapters") or [])
                                   if isinstance(a, dict)),
                    kv_cache_dtype=spec.get("kvCacheDtype"),
+                   weight_dtype=spec.get("weightDtype"),
                    speculative_tokens=spec.get("speculativeTokens"),
                    guided_decoding_states=spec.get("guidedDecodingStates"),
                    embedding_slots=spec.get("embeddingSlots"))
@@ -160,6 +164,15 @@ class ModelSpec:
                 errs.append(f"spec.kvCacheDtype must be one of {list(KV_CACHE_DTYPES)}, not {self.kv_cache_dtype!r}")
             elif self.kv_cache_dtype == "fp8" and int(self.expert_parallel or 1) > 1:
                 errs.append("spec.kvCacheDtype fp8 needs expertParallel = 1 (no fp8 KV cache for MoE / EP engines)")
+        if self.weight_dtype is not None:
+            if self.weight_dtype not in WEIGHT_DTYPES:
+                errs.append(f"spec.weightDtype must be one of {list(WEIGHT_DTYPES)}, not {self.weight_dtype!r}")
+            elif self.weight_dtype == "int4":
+                if int(self.tensor_parallel or 1) > 1 or int(self.expert_parallel or 1) > 1:
+                    errs.append("spec.weightDtype int4 needs tensorParallel = 1 and expertParallel = 1 "
+                                "(dense models on one GPU)")
+                if self.adapters:
+                    errs.append("spec.weightDtype int4 is not supported with adapters")
         k = self.speculative_tokens
         if k is not None:
             if isinstance(k, bool) or not isinstance(k, int) or not 0 <= k <= MAX_SPECULATIVE_TOKENS:

@@ -18,6 +18,15 @@ def kv_dtype_bytes(name: str) -> tuple[int, int]:
     return KV_CACHE_DTYPE_BYTES[name]
 
 
+WEIGHT_DTYPES = ("bf16", "int4")  # EngineConfig.weight_dtype / spec.weightDtype
+
+
+def weight_dtype_check(name: str) -> str:
+    if name not in WEIGHT_DTYPES:
+        raise ValueError(f"weight_dtype must be one of {sorted(WEIGHT_DTYPES)}, not {name!r}")
+    return name
+
+
 @dataclass(frozen=True)
 class ModelConfig:
     name: str
@@ -88,8 +97,24 @@ class ModelConfig:
         extra = self.num_layers * 3 * self.hidden_size * self.intermediate_size * (self.top_k - 1)
         return dense.num_params() + extra + self.num_layers * self.hidden_size * self.num_experts
 
-    def weight_bytes(self, dtype_bytes: int = 2) -> int:
-        return self.num_params() * dtype_bytes
+    def projection_shapes(self) -> tuple:
+        """(N, K) of a dense layer's qkv, o, gate_up and down projections."""
+        H, I = self.hidden_size, self.intermediate_size
+        return ((self.q_size + 2 * self.kv_size, H), (H, self.q_size), (2 * I, H), (H, I))
+
+    def weight_bytes(self, dtype_bytes: int = 2, weight_dtype: str | None = None) -> int:
+        """Bytes of the weights.  ``weight_dtype="int4"`` (dense models): the four projections of
+        every layer packed (N K / 2 nibble bytes + N K / 64 of bf16 group scales each), everything
+        else at ``dtype_bytes``, plus the bf16 dequantisation scratch of the largest projection."""
+        weight_dtype_check(weight_dtype or "bf16")
+        if weight_dtype != "int4":
+            return self.num_params() * dtype_bytes
+        if self.is_moe:
+            raise ValueError('weight_dtype="int4" is not supported for MoE models')
+        proj = [n * k for n, k in self.projection_shapes()]
+        packed = sum(p // 2 + p // 64 for p in proj)
+        rest = self.num_params() - self.num_layers * sum(proj)
+        return self.num_layers * packed + rest * dtype_bytes + 2 * max(proj)
 
     def kv_bytes_per_token(self, dtype_bytes: int = 2, kv_cache_dtype: str | None = None) -> int:
         """KV cache bytes of one token over all layers.  ``kv_cache_dtype`` ("bf16" / "fp8"): the

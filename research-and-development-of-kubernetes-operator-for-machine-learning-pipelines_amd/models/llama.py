@@ -65,6 +65,9 @@ class LlamaModel:
         # in_norm / post_norm weights all ones (random init, or after fold_norms()): the large-M
         # TP=1 forward may then run the norm chain (ops.gemm_res_ss / gemm_rs)
         self.unit_norms = True
+        # "int4" after quantize_int4(): the four projections of every layer are packed tuples
+        self.weight_dtype = "bf16"
+        self.q4_scratch_numel = 0
 
     # ---------------------------------------------------------- sharding --
     @torch.no_grad()
@@ -157,18 +160,55 @@ class LlamaModel:
     def weight_tensors(self):
         yield self.embed
         for L in self.layers:
-            yield from (v for v in L.values() if isinstance(v, torch.Tensor))
+            for v in L.values():
+                if isinstance(v, torch.Tensor):
+                    yield v
+                elif isinstance(v, tuple):  # a packed int4 projection (qw, qs, N, K)
+                    yield from v[:2]
         yield self.final_norm
         if self.lm_head is not self.embed:
             yield self.lm_head
 
     def weight_bytes(self) -> int:
-        return sum(t.numel() * t.element_size() for t in self.weight_tensors())
+        """Bytes of every weight tensor; an int4 model's include its dequantisation scratch."""
+        return sum(t.numel() * t.element_size() for t in self.weight_tensors()) + 2 * self.q4_scratch_numel
+
+    # ------------------------------------------------------- int4 weights --
+    Q4_PROJECTIONS = ("qkv", "o", "gate_up", "down")
+
+    @torch.no_grad()
+    def quantize_int4(self) -> "LlamaModel":
+        """Replace the qkv / o / gate_up / down weights of every layer by their int4 form
+        (ops.q4_quantize_pack: symmetric, one bf16 scale per row and 128 columns), one layer at a
+        time, each bf16 original freed before the next is quantised.  Embedding, LM head and norms
+        stay bf16.  The forward then runs ``_forward_q4``."""
+        if self.weight_dtype == "int4":
+            return self
+        if self.ps.tp_size > 1:
+            raise ValueError('weight_dtype="int4" needs tensor parallel size 1')
+        if self.cfg.is_moe:
+            raise ValueError('weight_dtype="int4" is not supported for MoE models')
+        largest = 0
+        for L in self.layers:
+            for name in self.Q4_PROJECTIONS:
+                largest = max(largest, L[name].numel())
+                L[name] = ops.q4_quantize_pack(L[name])  # ValueError unless N % 16 == 0 and K % 128 == 0
+        # the large-M route dequantises one projection at a time into this scratch
+        self.q4_scratch_numel = largest
+        ops.q4_reserve_scratch(self.device, largest)
+        if self.device.type == "cuda":  # hand the freed bf16 blocks back: the KV pool is sized from free HBM
+            torch.cuda.empty_cache()
+        self.weight_dtype = "int4"
+        return self
 
     def forward(self, ids: torch.Tensor, meta, kv, lora=None) -> torch.Tensor:
         """ids [T] int64; meta: AttnMeta (positions/slots/tables); kv: KVCache.
         Returns the final-normed hidden states of every token [T, H].  ``lora``: a
         ``models.lora.LoraStep`` when some token of the step uses an adapter."""
+        if self.weight_dtype == "int4":
+            if lora is not None:
+                raise ValueError("LoRA adapters are not served over int4 weights")
+            return self._forward_q4(ids, meta, kv)
         if lora is not None:
             return self._forward_lora(ids, meta, kv, lora)
         cfg, tp = self.cfg, self.ps.tp
@@ -248,6 +288,27 @@ class LlamaModel:
             x = ops.add_rmsnorm(o, residual, L["post_norm"], eps)
             act = ops.silu_mul(proj(x, L, S, "gate_up"), interleaved=True)
             d = proj(act, L, S, "down")
+            nxt = self.layers[i + 1]["in_norm"] if i + 1 < len(self.layers) else self.final_norm
+            x = ops.add_rmsnorm(d, residual, nxt, eps)
+        return x
+
+    def _forward_q4(self, ids, meta, kv) -> torch.Tensor:
+        """The int4-weights forward (TP = 1): the layer from its unfused blocks, every projection
+        through ops.gemm_q4 (the weight-streaming int4 kernel up to 64 rows; dequantise + the bf16
+        GEMMs above, where gate_up keeps its fused SiLU-mul).  The stand-alone RoPE + cache writers
+        serve QK-norm and fp8 KV as they do for bf16 weights."""
+        eps = self.cfg.rms_eps
+        residual = ops.embedding(ids, self.embed, self.vocab_start)
+        x = ops.rmsnorm(residual, self.layers[0]["in_norm"], eps)
+        for i, L in enumerate(self.layers):
+            qkn = {"q_norm": L["q_norm"], "k_norm": L["k_norm"], "eps": eps} if self.cfg.qk_norm else {}
+            q = ops.rope_cache(ops.gemm_q4(x, L["qkv"]), meta.positions, self.cos_sin, meta.slots, kv.k[i], kv.v[i],
+                               self.n_q, **qkn, **kv.scales(i))
+            a = ops.paged_attention(q, kv.k[i], kv.v[i], meta, **kv.scales(i))
+            o = ops.gemm_q4(a.view(a.shape[0], -1), L["o"])
+            x = ops.add_rmsnorm(o, residual, L["post_norm"], eps)
+            act = ops.gemm_q4(x, L["gate_up"], epi=ops.EPI_SILU_MUL)
+            d = ops.gemm_q4(act, L["down"])
             nxt = self.layers[i + 1]["in_norm"] if i + 1 < len(self.layers) else self.final_norm
             x = ops.add_rmsnorm(d, residual, nxt, eps)
         return x

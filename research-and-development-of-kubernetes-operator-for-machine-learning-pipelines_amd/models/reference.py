@@ -13,7 +13,18 @@ from ..ops import deinterleave_rows
 from ..ops import reference as ref
 
 
-def _mlp(model, i, x):
+def _proj(L, name, weight_dtype):
+    """fp32 weight of a dense projection.  ``weight_dtype="int4"``: through the int4 format and back
+    (``ref.q4_dequant(ref.q4_quantize(w))``); a projection the model already holds packed is unpacked."""
+    w = L[name]
+    if isinstance(w, tuple):
+        return ref.q4_dequant(*ref.q4_unpack(w[0], w[1])).float()
+    if weight_dtype == "int4":
+        return ref.q4_dequant(*ref.q4_quantize(w)).float()
+    return w.float()
+
+
+def _mlp(model, i, x, weight_dtype=None):
     L = model.layers[i]
     if model.cfg.is_moe:
         logits = F.linear(x, L["router"].float())
@@ -29,25 +40,30 @@ def _mlp(model, i, x):
             h = F.linear(ref.silu_mul(gu.to(model.dtype)).float(), L["w2"][e].float())
             out.index_add_(0, rows, h * w[rows, k, None])
         return out
-    gu = F.linear(x, deinterleave_rows(L["gate_up"]).float()).to(model.dtype)
-    return F.linear(ref.silu_mul(gu).float(), L["down"].float())
+    gu = F.linear(x, deinterleave_rows(_proj(L, "gate_up", weight_dtype))).to(model.dtype)
+    return F.linear(ref.silu_mul(gu).float(), _proj(L, "down", weight_dtype))
 
 
 @torch.no_grad()
-def dense_logits(model, tokens, kv_cache_dtype: str | None = None) -> torch.Tensor:
+def dense_logits(model, tokens, kv_cache_dtype: str | None = None, weight_dtype: str | None = None) -> torch.Tensor:
     """[T, V] fp32 logits of a single sequence (TP=1 models only): the LM head over ``dense_hidden``."""
-    return F.linear(dense_hidden(model, tokens, kv_cache_dtype), model.lm_head.float())
+    return F.linear(dense_hidden(model, tokens, kv_cache_dtype, weight_dtype), model.lm_head.float())
 
 
 @torch.no_grad()
-def dense_hidden(model, tokens, kv_cache_dtype: str | None = None) -> torch.Tensor:
+def dense_hidden(model, tokens, kv_cache_dtype: str | None = None, weight_dtype: str | None = None) -> torch.Tensor:
     """[T, H] fp32 final-normed hidden states of a single sequence (TP=1 models only): what the LM
     head and the embedding pooling read.  ``kv_cache_dtype="fp8"``: the
     post-RoPE K and the V rows go through the fp8 KV cache's format per (token, kv head)
     (``ops.reference.fp8_fake_quant``), the oracle of an engine with that cache; None / "bf16":
-    no quantisation."""
+    no quantisation.  ``weight_dtype="int4"``: the fake-quant oracle of an int4-weights engine, the
+    qkv / o / gate_up / down weights of a dense model through ``ref.q4_quantize`` and back."""
     if kv_cache_dtype not in (None, "bf16", "fp8"):
         raise ValueError(f"kv_cache_dtype {kv_cache_dtype!r}")
+    if weight_dtype not in (None, "bf16", "int4"):
+        raise ValueError(f"weight_dtype {weight_dtype!r}")
+    if weight_dtype == "int4" and model.cfg.is_moe:
+        raise ValueError('weight_dtype="int4" is not supported for MoE models')
     cfg = model.cfg
     dev = model.embed.device
     T = len(tokens)
@@ -62,7 +78,7 @@ def dense_hidden(model, tokens, kv_cache_dtype: str | None = None) -> torch.Tens
     if W > 0:  # query i sees the keys i - W < j <= i
         mask |= torch.tril(torch.ones(T, T, dtype=torch.bool, device=dev), -W)
     for i, L in enumerate(model.layers):
-        qkv = F.linear(x, L["qkv"].float())
+        qkv = F.linear(x, _proj(L, "qkv", weight_dtype))
         q = qkv[:, : model.n_q * D].view(T, model.n_q, D)
         k = qkv[:, model.n_q * D:(model.n_q + model.n_kv) * D].view(T, model.n_kv, D)
         v = qkv[:, (model.n_q + model.n_kv) * D:].view(T, model.n_kv, D)
@@ -79,9 +95,9 @@ def dense_hidden(model, tokens, kv_cache_dtype: str | None = None) -> torch.Tens
         s = torch.einsum("qhd,khd->hqk", q, k) / D ** 0.5
         s = s.masked_fill(mask[None], float("-inf"))
         a = torch.einsum("hqk,khd->qhd", s.softmax(-1), v).reshape(T, -1)
-        res = res + F.linear(a, L["o"].float())
+        res = res + F.linear(a, _proj(L, "o", weight_dtype))
         x = ref.rmsnorm(res, L["post_norm"].float(), cfg.rms_eps)
-        res = res + _mlp(model, i, x)
+        res = res + _mlp(model, i, x, weight_dtype)
         nxt = model.layers[i + 1]["in_norm"] if i + 1 < len(model.layers) else model.final_norm
         x = ref.rmsnorm(res, nxt.float(), cfg.rms_eps)
     return x

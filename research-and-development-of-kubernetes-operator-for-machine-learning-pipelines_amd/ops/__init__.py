@@ -747,6 +747,83 @@ def deinterleave_cols(y: torch.Tensor, group: int = 16) -> torch.Tensor:
     return torch.cat([v[:, :, 0].reshape(-1, n2 // 2), v[:, :, 1].reshape(-1, n2 // 2)], -1).view(*lead, n2)
 
 
+# --------------------------------------------------------- int4 weights --
+# W4A16 (csrc/gemm_q4.hip; the format is ref.q4_quantize's).  A packed weight is the tuple
+# W = (qw, qs, N, K) of ``q4_pack``.  Up to Q4_WS_MAX_M rows the weight-streaming int4 kernel runs;
+# above, the weight is dequantised into a bf16 scratch and the unchanged ``gemm`` takes it.
+Q4_WS_KERNEL_MAX_M = 64  # gemm_q4_kernel's MT limit (4 row tiles of 16)
+Q4_WS_MAX_M = min(Q4_WS_KERNEL_MAX_M, max(0, int(os.environ.get("MLOP_Q4_WS_MAX_M", "64"))))
+_Q4_SCRATCH: dict = {}
+
+
+def q4_pack(q: torch.Tensor, s: torch.Tensor):
+    """(q int8 [N, K], s bf16 [N, K / 128]) -> W = (qw, qs, N, K) in the kernel's layout."""
+    qw, qs = ref.q4_pack(q, s)
+    return qw, qs, int(q.shape[0]), int(q.shape[1])
+
+
+def q4_quantize_pack(w: torch.Tensor):
+    """bf16 [N, K] -> packed W (ref.q4_quantize, then the layout), on w's device."""
+    return q4_pack(*ref.q4_quantize(w))
+
+
+def q4_bytes(N: int, K: int) -> int:
+    """Bytes of a packed [N, K] projection: nibbles + one bf16 scale per 128."""
+    return N * K // 2 + N * K // 64
+
+
+def q4_reserve_scratch(device, numel: int) -> torch.Tensor:
+    """The dequantisation scratch of ``device`` (bf16, >= numel elements): one fixed buffer that only
+    grows outside graph capture, read and written in stream order."""
+    device = torch.device(device)
+    buf = _Q4_SCRATCH.get(device)
+    if buf is None or buf.numel() < numel:
+        if device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("int4 dequant scratch too small inside a graph capture: call q4_reserve_scratch first")
+        buf = _Q4_SCRATCH[device] = torch.empty(numel, dtype=torch.bfloat16, device=device)
+    return buf
+
+
+def q4_dequant(W, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Packed W -> bf16 [N, K] row-major, bit-equal to ``ref.q4_dequant``."""
+    qw, qs, N, K = W
+    if not qw.is_cuda:
+        y = ref.q4_dequant(*ref.q4_unpack(qw, qs))
+        if out is not None:
+            out.copy_(y)
+            return out
+        return y
+    _need_gpu()
+    out = torch.empty(N, K, dtype=torch.bfloat16, device=qw.device) if out is None else out
+    torch.ops.mlop.q4_dequant(out, qw, qs)
+    return out
+
+
+def gemm_q4(x: torch.Tensor, W, epi: int = EPI_NONE) -> torch.Tensor:
+    """y = epi(x @ dequant(W)^T) for a packed int4 W.  M <= Q4_WS_MAX_M: gemm_q4.hip (per group the
+    exact integer dot products, scaled in fp32; ``ref.gemm_q4``), SiLU-mul as the separate
+    interleaved kernel.  Larger M: dequantise, then ``gemm(x, scratch, epi)``."""
+    qw, qs, N, K = W
+    if x.shape[-1] != K:
+        raise ValueError(f"gemm_q4: x has {x.shape[-1]} columns, the weight K = {K}")
+    lead = x.shape[:-1]
+    x2 = x.reshape(-1, K)
+    if not x.is_cuda:
+        return gemm(x2, q4_dequant(W), epi=epi).view(*lead, -1)
+    M = x2.shape[0]
+    if M > Q4_WS_MAX_M or M == 0:
+        wd = q4_dequant(W, q4_reserve_scratch(x.device, N * K)[: N * K].view(N, K))
+        return gemm(x2, wd, epi=epi).view(*lead, -1)
+    _need_gpu()
+    if x2.stride(-1) != 1 or x2.stride(0) % 8:
+        x2 = x2.contiguous()
+    y = torch.empty(M, N, dtype=x.dtype, device=x.device)
+    torch.ops.mlop.gemm_q4(y, x2, qw, qs, N)
+    if epi == EPI_SILU_MUL:
+        y = silu_mul(y, interleaved=True)
+    return y.view(*lead, -1)
+
+
 def argmax(logits: torch.Tensor) -> torch.Tensor:
     if not logits.is_cuda:
         return logits.argmax(-1)

@@ -84,9 +84,10 @@ def _stale(obj: Path, src: Path, headers, cmd) -> tuple[bool, str]:
 # (MI355X_MICROARCH.md, per-instruction constants).
 _ATTN_FLAGS = ["-fno-honor-nans", "-fno-slp-vectorize"]
 # moe_wide: no packed fp32 instructions at all (v_pk_add_f32 / v_pk_mul_f32 / v_pk_fma_f32): its
-# softmax and top-k epilogue is 32 independent fp32 values per lane, exactly what the vectoriser pairs up
+# softmax and top-k epilogue is 32 independent fp32 values per lane, exactly what the vectoriser pairs up;
+# gemm_q4: the same for its acc += s * gacc of four adjacent accumulator elements
 _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-FILE_FLAGS = {"attention": _ATTN_FLAGS, "moe_wide": _NO_PK_F32}
+FILE_FLAGS = {"attention": _ATTN_FLAGS, "moe_wide": _NO_PK_F32, "gemm_q4": _NO_PK_F32}
 
 
 def _run(cmd):

@@ -641,6 +641,44 @@ bool gemm_ws(Tensor out, Tensor a, Tensor w, int64_t epi, bool rs, double eps) {
   return true;
 }
 
+// int4 weights (gemm_q4.hip): qw int32 [N / 16, K / 128, 64, 4] + qs bf16 [N / 16, K / 128, 16] (ops.q4_pack)
+static void check_q4(const Tensor& qw, const Tensor& qs, int64_t N, int64_t K) {
+  TORCH_CHECK(N >= 16 && N % 16 == 0 && K >= 128 && K % 128 == 0, "int4 weights need N % 16 == 0 and K % 128 == 0, not N = ",
+              N, ", K = ", K);
+  TORCH_CHECK(qw.is_cuda() && qw.scalar_type() == at::kInt && qw.is_contiguous() && qw.numel() == N * K / 8,
+              "qw must be int32 [N / 16, K / 128, 64, 4] on the GPU");
+  check_bf16(qs, "qs");
+  TORCH_CHECK(qs.numel() == N * K / 128, "qs must be bf16 [N / 16, K / 128, 16]");
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(qw.data_ptr()) & 15) == 0, "qw must be 16-B aligned");
+}
+
+void gemm_q4(Tensor out, Tensor a, Tensor qw, Tensor qs, int64_t N, int64_t rb) {
+  check_a(a);
+  const int64_t M = a.size(0), K = a.size(1);
+  check_q4(qw, qs, N, K);
+  TORCH_CHECK(M >= 1 && M <= 64, "gemm_q4: 1 <= M <= 64 (ops.gemm_q4 dequantises above), not ", M);
+  TORCH_CHECK(out.is_cuda() && out.scalar_type() == at::kBFloat16 && out.dim() == 2 && out.size(0) == M &&
+                  out.size(1) == N && out.stride(1) == 1 && out.device() == a.device() && qw.device() == a.device() &&
+                  qs.device() == a.device(), "gemm_q4: out bf16 [M, N] on a's device");
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(a.data_ptr()) & 15) == 0, "a must be 16-B aligned");
+  c10::DeviceGuard g(a.device());
+  TORCH_CHECK(mlop::launch_gemm_q4(a.data_ptr(), (int)a.stride(0), qw.data_ptr(), qs.data_ptr(), out.data_ptr(),
+                                   (int)out.stride(0), (int)M, (int)N, (int)K, (int)rb, cur_stream()),
+              "gemm_q4: shape or rb refused");
+}
+
+void q4_dequant(Tensor out, Tensor qw, Tensor qs) {
+  check_bf16(out, "out");
+  TORCH_CHECK(out.dim() == 2, "q4_dequant: out bf16 [N, K]");
+  const int64_t N = out.size(0), K = out.size(1);
+  check_q4(qw, qs, N, K);
+  TORCH_CHECK(qw.device() == out.device() && qs.device() == out.device(), "q4_dequant: one device");
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(out.data_ptr()) & 15) == 0, "out must be 16-B aligned");
+  c10::DeviceGuard g(out.device());
+  TORCH_CHECK(mlop::launch_q4_dequant(out.data_ptr(), qw.data_ptr(), qs.data_ptr(), (int)N, (int)K, cur_stream()),
+              "q4_dequant: shape refused");
+}
+
 void gemm_ws_plan(int64_t rb, int64_t u, int64_t nt) { mlop::gemm_ws_plan((int)rb, (int)u, (int)nt); }
 
 // grouped (MoE): rows of a sorted by group, offsets [G+1]; w [G, N, K]
@@ -1345,6 +1383,8 @@ TORCH_LIBRARY(mlop, m) {
         "Tensor slot_rank) -> ()");
   m.def("embedding(Tensor(a!) out, Tensor table, Tensor ids, int vocab_start) -> ()");
   m.def("gemm_ws(Tensor(a!) out, Tensor a, Tensor w, int epi, bool rs, float eps) -> bool");
+  m.def("gemm_q4(Tensor(a!) out, Tensor a, Tensor qw, Tensor qs, int N, int rb=0) -> ()");
+  m.def("q4_dequant(Tensor(a!) out, Tensor qw, Tensor qs) -> ()");
   m.def("flash_prefill(Tensor(a!) out, Tensor q, Tensor k_cache, Tensor v_cache, Tensor block_tables, "
         "Tensor ptile_seq, Tensor ptile_q0, Tensor q_start, Tensor q_len, Tensor ctx_len, float scale, "
         "int window=0) -> ()");
@@ -1381,6 +1421,8 @@ TORCH_LIBRARY_IMPL(mlop, CUDA, m) {
   m.impl("flash_prefill", &flash_prefill);
   m.impl("gemm", &gemm);
   m.impl("gemm_ws", &gemm_ws);
+  m.impl("gemm_q4", &gemm_q4);
+  m.impl("q4_dequant", &q4_dequant);
   m.impl("grouped_gemm", &grouped_gemm);
   m.impl("gemm_add_rmsnorm", &gemm_add_rmsnorm);
   m.impl("gemm_res_ss", &gemm_res_ss);

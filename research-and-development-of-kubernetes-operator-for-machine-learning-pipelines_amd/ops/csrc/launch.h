@@ -139,6 +139,13 @@ struct NormPro {
 void gemm_ws_plan(int rb, int u, int nt);
 void launch_ws(const void* A, int lda, const void* B, int ldb, void* C, int ldc, int M, int N, int K, int epi,
                bool rs, const RopeEpi& re, float eps, hipStream_t st);
+// int4 weights (gemm_q4.hip): qw uint32 [N / 16, K / 128, 64, 4] + qs bf16 [N / 16, K / 128, 16]
+// (ops.q4_pack).  C = A . W^T at 1 <= M <= 64 (plain bf16 store); the dequantiser writes bf16 [N, K].
+// rb: 16-row blocks per workgroup (1 / 2 / 4 with 16 rb | N; 0 = by N).  false = shape refused (K % 128,
+// N % 16, M, rb), nothing launched
+bool launch_gemm_q4(const void* A, int lda, const void* qw, const void* qs, void* C, int ldc, int M, int N, int K,
+                    int rb, hipStream_t st);
+bool launch_q4_dequant(void* out, const void* qw, const void* qs, int N, int K, hipStream_t st);
 void launch_gemv_rs(const void* A, int lda, const void* B, void* C, int ldc, int M, int N, int K, int epi,
                     const RopeEpi& re, float eps, hipStream_t st);
 void launch_gemv_res(const void* A, int lda, const void* B, void* residual, int M, int N, int K, hipStream_t st);

@@ -196,6 +196,70 @@ def paged_attention(q, k_cache, v_cache, meta, k_scale=None, v_scale=None):
     return out
 
 
+# --------------------------------------------------------- int4 weights --
+# W4A16: symmetric int4, one bf16 scale per (weight row, 128-wide K group).  s = bf16(amax / 7),
+# q = clamp(round_half_even(w / float(s)), -8, 7); an all-zero group has s = 0, q = 0.
+Q4_GROUP = 128
+
+
+def _q4_check(N: int, K: int) -> None:
+    if N < 16 or N % 16 or K < Q4_GROUP or K % Q4_GROUP:
+        raise ValueError(f"int4 weights need N % 16 == 0 and K % {Q4_GROUP} == 0, not [N = {N}, K = {K}]")
+
+
+def q4_quantize(w: torch.Tensor):
+    """w [N, K] -> (q int8 [N, K] in [-8, 7], s bf16 [N, K / 128])."""
+    N, K = w.shape
+    _q4_check(N, K)
+    wg = w.float().view(N, K // Q4_GROUP, Q4_GROUP)
+    s = (wg.abs().amax(-1) / 7).to(torch.bfloat16)
+    sf = s.float()[..., None]
+    q = torch.where(sf > 0, torch.round(wg / torch.where(sf > 0, sf, torch.ones_like(sf))), torch.zeros_like(wg))
+    return q.clamp_(-8, 7).to(torch.int8).view(N, K), s
+
+
+def q4_dequant(q: torch.Tensor, s: torch.Tensor) -> torch.Tensor:
+    """bf16(float(s) * q) [N, K]: exact as defined (an 11-bit product, rounded once)."""
+    return (s.float().repeat_interleave(Q4_GROUP, dim=1) * q.float()).to(torch.bfloat16)
+
+
+def gemm_q4(x: torch.Tensor, q: torch.Tensor, s: torch.Tensor, dtype=torch.float64) -> torch.Tensor:
+    """y[m, n] = bf16(sum_g float(s[n, g]) * sum_{k in g} q[n, k] x[m, k]); the sums in ``dtype``."""
+    N, K = q.shape
+    G = K // Q4_GROUP
+    part = torch.einsum("mgk,ngk->mng", x.to(dtype).view(-1, G, Q4_GROUP), q.to(dtype).view(N, G, Q4_GROUP))
+    return (part * s.to(dtype)[None]).sum(-1).to(torch.bfloat16)
+
+
+def q4_pack(q: torch.Tensor, s: torch.Tensor):
+    """The device layout of csrc/gemm_q4.hip: (qw int32 [N / 16, K / 128, 64, 4], qs bf16
+    [N / 16, K / 128, 16]).  Lane l's 4 words of tile (nb, g) hold weight row 16 nb + (l & 15); word
+    j the chunk k = 128 g + 32 j + 8 (l >> 4) + e, e = 0..7, element e as u = q + 8 at nibble
+    (e >> 1) + 4 (e & 1).  (int32 holds the uint32 bit patterns: torch has no uint32 arithmetic.)"""
+    N, K = q.shape
+    _q4_check(N, K)
+    G = K // Q4_GROUP
+    u = (q.to(torch.int64) + 8).view(N // 16, 16, G, 4, 4, 8)       # nb, row, g, j, chunk (l >> 4), e
+    u = u.permute(0, 2, 4, 1, 3, 5)                                 # nb, g, chunk, row, j, e: lane = 16 chunk + row
+    e = torch.arange(8, device=q.device)
+    word = (u << (4 * ((e >> 1) + 4 * (e & 1)))).sum(-1)            # < 2^32
+    word = torch.where(word >= 2 ** 31, word - 2 ** 32, word).to(torch.int32)
+    qw = word.reshape(N // 16, G, 64, 4).contiguous()
+    qs = s.view(N // 16, 16, G).permute(0, 2, 1).contiguous()
+    return qw, qs
+
+
+def q4_unpack(qw: torch.Tensor, qs: torch.Tensor):
+    """The inverse of ``q4_pack``: (q int8 [N, K], s bf16 [N, K / 128])."""
+    NB, G = qw.shape[0], qw.shape[1]
+    e = torch.arange(8, device=qw.device)
+    w = qw.to(torch.int64) & 0xFFFFFFFF
+    u = (w[..., None] >> (4 * ((e >> 1) + 4 * (e & 1)))) & 15       # nb, g, lane, j, e
+    u = u.view(NB, G, 4, 16, 4, 8).permute(0, 3, 1, 4, 2, 5)        # nb, row, g, j, chunk, e
+    q = (u - 8).to(torch.int8).reshape(NB * 16, G * Q4_GROUP)
+    return q, qs.permute(0, 2, 1).reshape(NB * 16, G).contiguous()
+
+
 # ------------------------------------------------------------------ MoE --
 
 def moe_route(logits, top_k, renorm=True):

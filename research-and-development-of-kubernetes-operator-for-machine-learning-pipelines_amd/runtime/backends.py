@@ -88,6 +88,7 @@ class LLMBackend:
         self.steps = 0
         if metrics is not None:
             metrics.kv_dtype.labels(**metrics.lv(dtype=self._kv_dtype())).set(1)
+            metrics.weight_dtype.labels(**metrics.lv(dtype=self._weight_dtype())).set(1)
         from .gpu_metrics import KernelTimeSampler
 
         # one profiled engine step per period -> mlop_kernel_time_fraction{kernel=...}
@@ -233,10 +234,13 @@ class LLMBackend:
     def _kv_dtype(self) -> str:
         return str(getattr(getattr(self.engine, "cfg", None), "kv_cache_dtype", "bf16"))
 
+    def _weight_dtype(self) -> str:
+        return str(getattr(getattr(self.engine, "cfg", None), "weight_dtype", "bf16"))
+
     def metadata(self) -> dict:
         cfg = self.engine.model.cfg
         md = {"name": self.name, "platform": "mlopamd-llm-rocm", "architecture": cfg.name,
-              "kv_cache_dtype": self._kv_dtype(),
+              "kv_cache_dtype": self._kv_dtype(), "weight_dtype": self._weight_dtype(),
               "inputs": [{"name": "text_input", "datatype": "BYTES", "shape": [-1]},
                          {"name": "input_ids", "datatype": "INT64", "shape": [-1]}],
               "outputs": [{"name": "text_output", "datatype": "BYTES", "shape": [-1]},

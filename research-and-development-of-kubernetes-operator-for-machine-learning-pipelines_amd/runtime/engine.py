@@ -52,6 +52,7 @@ import numpy as np
 import torch
 
 from .. import ops
+from ..models.config import weight_dtype_check
 from .attn_meta import MetaBuffers, plan_partitions
 from .kv_cache import (BLOCK_SIZE, KV_DTYPES, BlockAllocator, KVCache, blocks_for_budget, blocks_needed,
                        kv_dtype_bytes, prefix_hashes)
@@ -258,6 +259,11 @@ class EngineConfig:
     # 2 D / (D + 1) = 1.98x the pages per byte.  fp8 has no sliding-window, flash-prefill, MoE or
     # fused-epilogue kernels: those models are rejected, prompt chunks run on the 16-row tiles.
     kv_cache_dtype: str = "bf16"
+    # element type of the qkv / o / gate_up / down weights: "bf16", or "int4" = symmetric 4-bit
+    # values with one bf16 scale per (row, 128 columns) (ops/reference.py "int4 weights"), quantised
+    # on the device once the weights are loaded: 3.9x fewer projection bytes.  Dense TP = 1 models
+    # without LoRA; embedding, LM head and norms stay bf16.  "bf16" changes no launch or allocation.
+    weight_dtype: str = "bf16"
     # speculative decoding by prompt lookup (runtime/spec.py): up to ``spec_tokens`` (k <= 7) draft
     # tokens per row, found by matching the sequence's last ``spec_ngram_max`` .. ``spec_ngram_min``
     # tokens in its own history, are verified in one pass with the row's decode token; outputs are
@@ -412,6 +418,14 @@ class Engine:
                 raise ValueError('kv_cache_dtype="fp8" is not supported for MoE models / expert parallelism')
             if mc.head_dim != 128:
                 raise ValueError('kv_cache_dtype="fp8" needs head_dim 128')
+        if weight_dtype_check(cfg.weight_dtype) == "int4":  # ValueError for an unknown name
+            if model.ps.tp.size > 1:
+                raise ValueError('weight_dtype="int4" needs tensor parallel size 1')
+            if getattr(mc, "is_moe", False) or model.ps.ep.size > 1:
+                raise ValueError('weight_dtype="int4" is not supported for MoE models / expert parallelism')
+            if cfg.max_adapters > 0:
+                raise ValueError('weight_dtype="int4" does not serve LoRA adapters (max_adapters must be 0)')
+            model.quantize_int4()  # before anything below sizes itself from the free memory
         self.spec_k = int(cfg.spec_tokens or 0)
         # optional callable (seq, cap) -> list[int]: replaces the device n-gram proposals (the
         # extension point of a draft-model proposer; lets tests force any acceptance pattern)
@@ -533,6 +547,8 @@ class Engine:
             # (only when it is not the default: the other entries are counters that callers
             # difference between two readings; read it as stats.get("kv_cache_dtype", "bf16"))
             self.stats["kv_cache_dtype"] = cfg.kv_cache_dtype
+        if cfg.weight_dtype != "bf16":  # likewise: stats.get("weight_dtype", "bf16")
+            self.stats["weight_dtype"] = cfg.weight_dtype
         # one-step-ahead (async) scheduling state: the in-flight step, its token read-back
         # buffers (two pinned, alternating) and the event after its metadata upload.  Under TP
         # only the leader schedules (workers follow the host-side headers, StepSync); under EP
