@@ -87,7 +87,7 @@ class CanaryPolicy:
 
 
 KV_CACHE_DTYPES = ("bf16", "fp8")  # spec.kvCacheDtype (manifests/crd.yaml's enum)
-WEIGHT_DTYPES = ("bf16", "int4")  # spec.weightDtype (manifests/crd.yaml's enum)
+WEIGHT_DTYPES = ("bf16", "int4", "mxfp4")  # spec.weightDtype (manifests/crd.yaml's enum)
 MAX_SPECULATIVE_TOKENS = 7         # spec.speculativeTokens (manifests/crd.yaml's maximum; runtime/spec.py)
 MAX_GUIDED_STATES = 32767          # spec.guidedDecodingStates (int16 arena entries; runtime/guided.py)
 MAX_EMBEDDING_SLOTS = 4096         # spec.embeddingSlots (manifests/crd.yaml's maximum; EngineConfig.embed_slots)
@@ -112,7 +112,8 @@ class ModelSpec:
     adapters: tuple = ()
     # KV cache element type of the LLM runtime: None / "bf16", or "fp8" (e4m3fn pages + row scales)
     kv_cache_dtype: str | None = None
-    # projection weights of the LLM runtime: None / "bf16", or "int4" (group-128 symmetric, quantised at load)
+    # projection weights of the LLM runtime: None / "bf16", "int4" (group-128 symmetric) or "mxfp4"
+    # (e2m1 + one e8m0 scale per 32), both quantised at load
     weight_dtype: str | None = None
     # draft tokens per step of the LLM runtime's prompt-lookup speculative decoding: None / 0 = off, 1..7
     speculative_tokens: int | None = None
@@ -167,12 +168,12 @@ class ModelSpec:
         if self.weight_dtype is not None:
             if self.weight_dtype not in WEIGHT_DTYPES:
                 errs.append(f"spec.weightDtype must be one of {list(WEIGHT_DTYPES)}, not {self.weight_dtype!r}")
-            elif self.weight_dtype == "int4":
+            elif self.weight_dtype != "bf16":
                 if int(self.tensor_parallel or 1) > 1 or int(self.expert_parallel or 1) > 1:
-                    errs.append("spec.weightDtype int4 needs tensorParallel = 1 and expertParallel = 1 "
-                                "(dense models on one GPU)")
+                    errs.append(f"spec.weightDtype {self.weight_dtype} needs tensorParallel = 1 and "
+                                "expertParallel = 1 (dense models on one GPU)")
                 if self.adapters:
-                    errs.append("spec.weightDtype int4 is not supported with adapters")
+                    errs.append(f"spec.weightDtype {self.weight_dtype} is not supported with adapters")
         k = self.speculative_tokens
         if k is not None:
             if isinstance(k, bool) or not isinstance(k, int) or not 0 <= k <= MAX_SPECULATIVE_TOKENS:

@@ -55,7 +55,7 @@ def plan(arch: str | ModelConfig, max_model_len: int = 4096, max_num_seqs: int =
     engine's KV cache format; the KV target and capacity use its bytes per token, scale bytes
     included (None: bf16).  ``grammar_states``: rows of the guided-decoding arena (int16
     [states, vocab]), charged states x vocab x 2 bytes beside the weights.  ``weight_dtype``
-    ("bf16" / "int4"): int4 weights (``ModelConfig.weight_bytes(weight_dtype=)``: packed projections,
+    ("bf16" / "int4" / "mxfp4"): 4-bit weights (``ModelConfig.weight_bytes(weight_dtype=)``: packed projections,
     scales and the dequantisation scratch) are planned on one GPU only; they are not sharded."""
     p = _plan(arch, max_model_len, max_num_seqs, hbm_gb, gpus_per_node, utilization, reserve_gb,
               requested_tp, requested_ep, kv_target_fraction, kv_cache_dtype, grammar_states, weight_dtype)
@@ -70,8 +70,8 @@ def _plan(arch, max_model_len, max_num_seqs, hbm_gb, gpus_per_node, utilization,
           requested_ep, kv_target_fraction, kv_cache_dtype=None, grammar_states=0, weight_dtype=None) -> Placement:
     cfg = arch if isinstance(arch, ModelConfig) else get_config(arch)
     usable = hbm_gb * utilization
-    int4 = weight_dtype == "int4"
-    wbytes = cfg.weight_bytes(weight_dtype=None if int4 and cfg.is_moe else weight_dtype)
+    w4 = weight_dtype in ("int4", "mxfp4")
+    wbytes = cfg.weight_bytes(weight_dtype=None if w4 and cfg.is_moe else weight_dtype)
     kv_tok = cfg.kv_bytes_per_token(kv_cache_dtype=kv_cache_dtype or "bf16")
     kv_target = max_num_seqs * max_model_len * kv_tok * kv_target_fraction
     arena = int(grammar_states or 0) * cfg.vocab_size * 2  # guided decoding: int16 [states, vocab]
@@ -88,10 +88,10 @@ def _plan(arch, max_model_len, max_num_seqs, hbm_gb, gpus_per_node, utilization,
                          hbm_gb, fits, "" if fits else
                          f"needs {round((w + arena + kv_per_gpu) / GB + reserve_gb, 1)} GB/GPU > {round(usable, 1)}")
 
-    if int4:  # one GPU or nothing: the int4 projections are not sharded, MoE experts not quantised
+    if w4:  # one GPU or nothing: the packed projections are not sharded, MoE experts not quantised
         p = evaluate(1, 1)
         if cfg.is_moe or int(requested_tp or 1) > 1 or int(requested_ep or 1) > 1:
-            p.fits, p.reason = False, f"weightDtype int4 serves dense models at tensorParallel = expertParallel = 1 ({cfg.name})"
+            p.fits, p.reason = False, f"weightDtype {weight_dtype} serves dense models at tensorParallel = expertParallel = 1 ({cfg.name})"
         return p
     if requested_tp:
         if not _valid_tp(cfg, requested_tp) or requested_tp > gpus_per_node:

@@ -18,7 +18,7 @@ def kv_dtype_bytes(name: str) -> tuple[int, int]:
     return KV_CACHE_DTYPE_BYTES[name]
 
 
-WEIGHT_DTYPES = ("bf16", "int4")  # EngineConfig.weight_dtype / spec.weightDtype
+WEIGHT_DTYPES = ("bf16", "int4", "mxfp4")  # EngineConfig.weight_dtype / spec.weightDtype
 
 
 def weight_dtype_check(name: str) -> str:
@@ -105,14 +105,15 @@ class ModelConfig:
     def weight_bytes(self, dtype_bytes: int = 2, weight_dtype: str | None = None) -> int:
         """Bytes of the weights.  ``weight_dtype="int4"`` (dense models): the four projections of
         every layer packed (N K / 2 nibble bytes + N K / 64 of bf16 group scales each), everything
-        else at ``dtype_bytes``, plus the bf16 dequantisation scratch of the largest projection."""
+        else at ``dtype_bytes``, plus the bf16 dequantisation scratch of the largest projection.
+        ``"mxfp4"``: likewise with N K / 2 + N K / 32 (one scale byte per 32) per projection."""
         weight_dtype_check(weight_dtype or "bf16")
-        if weight_dtype != "int4":
+        if weight_dtype not in ("int4", "mxfp4"):
             return self.num_params() * dtype_bytes
         if self.is_moe:
-            raise ValueError('weight_dtype="int4" is not supported for MoE models')
+            raise ValueError(f'weight_dtype="{weight_dtype}" is not supported for MoE models')
         proj = [n * k for n, k in self.projection_shapes()]
-        packed = sum(p // 2 + p // 64 for p in proj)
+        packed = sum(p // 2 + (p // 64 if weight_dtype == "int4" else p // 32) for p in proj)
         rest = self.num_params() - self.num_layers * sum(proj)
         return self.num_layers * packed + rest * dtype_bytes + 2 * max(proj)
 

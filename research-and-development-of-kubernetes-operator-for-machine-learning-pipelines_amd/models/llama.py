@@ -65,7 +65,8 @@ class LlamaModel:
         # in_norm / post_norm weights all ones (random init, or after fold_norms()): the large-M
         # TP=1 forward may then run the norm chain (ops.gemm_res_ss / gemm_rs)
         self.unit_norms = True
-        # "int4" after quantize_int4(): the four projections of every layer are packed tuples
+        # "int4" after quantize_int4(): the four projections of every layer are packed tuples;
+        # "mxfp4" after quantize_mxfp4(): they are ops.Mx4Weight
         self.weight_dtype = "bf16"
         self.q4_scratch_numel = 0
 
@@ -165,12 +166,14 @@ class LlamaModel:
                     yield v
                 elif isinstance(v, tuple):  # a packed int4 projection (qw, qs, N, K)
                     yield from v[:2]
+                elif isinstance(v, ops.Mx4Weight):
+                    yield from (v.qw, v.qe)
         yield self.final_norm
         if self.lm_head is not self.embed:
             yield self.lm_head
 
     def weight_bytes(self) -> int:
-        """Bytes of every weight tensor; an int4 model's include its dequantisation scratch."""
+        """Bytes of every weight tensor; an int4 / mxfp4 model's include its dequantisation scratch."""
         return sum(t.numel() * t.element_size() for t in self.weight_tensors()) + 2 * self.q4_scratch_numel
 
     # ------------------------------------------------------- int4 weights --
@@ -182,32 +185,43 @@ class LlamaModel:
         (ops.q4_quantize_pack: symmetric, one bf16 scale per row and 128 columns), one layer at a
         time, each bf16 original freed before the next is quantised.  Embedding, LM head and norms
         stay bf16.  The forward then runs ``_forward_q4``."""
-        if self.weight_dtype == "int4":
+        return self._quantize_w4("int4", ops.q4_quantize_pack)
+
+    @torch.no_grad()
+    def quantize_mxfp4(self) -> "LlamaModel":
+        """Likewise into MXFP4 (ops.mx4_quantize_pack: e2m1 codes, one e8m0 scale byte per row and
+        32 columns); a projection is then an ``ops.Mx4Weight``, not a tuple."""
+        return self._quantize_w4("mxfp4", ops.mx4_quantize_pack)
+
+    def _quantize_w4(self, name: str, quantize_pack) -> "LlamaModel":
+        if self.weight_dtype == name:
             return self
+        if self.weight_dtype != "bf16":
+            raise ValueError(f'weight_dtype="{name}": the weights are {self.weight_dtype} already')
         if self.ps.tp_size > 1:
-            raise ValueError('weight_dtype="int4" needs tensor parallel size 1')
+            raise ValueError(f'weight_dtype="{name}" needs tensor parallel size 1')
         if self.cfg.is_moe:
-            raise ValueError('weight_dtype="int4" is not supported for MoE models')
+            raise ValueError(f'weight_dtype="{name}" is not supported for MoE models')
         largest = 0
         for L in self.layers:
-            for name in self.Q4_PROJECTIONS:
-                largest = max(largest, L[name].numel())
-                L[name] = ops.q4_quantize_pack(L[name])  # ValueError unless N % 16 == 0 and K % 128 == 0
+            for proj in self.Q4_PROJECTIONS:
+                largest = max(largest, L[proj].numel())
+                L[proj] = quantize_pack(L[proj])  # ValueError unless N % 16 == 0 and K % 128 == 0
         # the large-M route dequantises one projection at a time into this scratch
         self.q4_scratch_numel = largest
         ops.q4_reserve_scratch(self.device, largest)
         if self.device.type == "cuda":  # hand the freed bf16 blocks back: the KV pool is sized from free HBM
             torch.cuda.empty_cache()
-        self.weight_dtype = "int4"
+        self.weight_dtype = name
         return self
 
     def forward(self, ids: torch.Tensor, meta, kv, lora=None) -> torch.Tensor:
         """ids [T] int64; meta: AttnMeta (positions/slots/tables); kv: KVCache.
         Returns the final-normed hidden states of every token [T, H].  ``lora``: a
         ``models.lora.LoraStep`` when some token of the step uses an adapter."""
-        if self.weight_dtype == "int4":
+        if self.weight_dtype != "bf16":
             if lora is not None:
-                raise ValueError("LoRA adapters are not served over int4 weights")
+                raise ValueError(f"LoRA adapters are not served over {self.weight_dtype} weights")
             return self._forward_q4(ids, meta, kv)
         if lora is not None:
             return self._forward_lora(ids, meta, kv, lora)
@@ -293,22 +307,23 @@ class LlamaModel:
         return x
 
     def _forward_q4(self, ids, meta, kv) -> torch.Tensor:
-        """The int4-weights forward (TP = 1): the layer from its unfused blocks, every projection
-        through ops.gemm_q4 (the weight-streaming int4 kernel up to 64 rows; dequantise + the bf16
-        GEMMs above, where gate_up keeps its fused SiLU-mul).  The stand-alone RoPE + cache writers
-        serve QK-norm and fp8 KV as they do for bf16 weights."""
+        """The 4-bit-weights forward (TP = 1): the layer from its unfused blocks, every projection
+        through ops.gemm_q4 or, for MXFP4 weights, ops.gemm_mx4 (the weight-streaming kernel up to
+        64 rows; dequantise + the bf16 GEMMs above, where gate_up keeps its fused SiLU-mul).  The
+        stand-alone RoPE + cache writers serve QK-norm and fp8 KV as they do for bf16 weights."""
         eps = self.cfg.rms_eps
+        gemm = ops.gemm_mx4 if self.weight_dtype == "mxfp4" else ops.gemm_q4
         residual = ops.embedding(ids, self.embed, self.vocab_start)
         x = ops.rmsnorm(residual, self.layers[0]["in_norm"], eps)
         for i, L in enumerate(self.layers):
             qkn = {"q_norm": L["q_norm"], "k_norm": L["k_norm"], "eps": eps} if self.cfg.qk_norm else {}
-            q = ops.rope_cache(ops.gemm_q4(x, L["qkv"]), meta.positions, self.cos_sin, meta.slots, kv.k[i], kv.v[i],
+            q = ops.rope_cache(gemm(x, L["qkv"]), meta.positions, self.cos_sin, meta.slots, kv.k[i], kv.v[i],
                                self.n_q, **qkn, **kv.scales(i))
             a = ops.paged_attention(q, kv.k[i], kv.v[i], meta, **kv.scales(i))
-            o = ops.gemm_q4(a.view(a.shape[0], -1), L["o"])
+            o = gemm(a.view(a.shape[0], -1), L["o"])
             x = ops.add_rmsnorm(o, residual, L["post_norm"], eps)
-            act = ops.gemm_q4(x, L["gate_up"], epi=ops.EPI_SILU_MUL)
-            d = ops.gemm_q4(act, L["down"])
+            act = gemm(x, L["gate_up"], epi=ops.EPI_SILU_MUL)
+            d = gemm(act, L["down"])
             nxt = self.layers[i + 1]["in_norm"] if i + 1 < len(self.layers) else self.final_norm
             x = ops.add_rmsnorm(d, residual, nxt, eps)
         return x

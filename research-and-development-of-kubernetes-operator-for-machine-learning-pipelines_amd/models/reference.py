@@ -14,13 +14,18 @@ from ..ops import reference as ref
 
 
 def _proj(L, name, weight_dtype):
-    """fp32 weight of a dense projection.  ``weight_dtype="int4"``: through the int4 format and back
-    (``ref.q4_dequant(ref.q4_quantize(w))``); a projection the model already holds packed is unpacked."""
+    """fp32 weight of a dense projection.  ``weight_dtype="int4"`` / ``"mxfp4"``: through that format
+    and back (``ref.q4_dequant(ref.q4_quantize(w))``, ``ref.mx4_dequant(ref.mx4_quantize(w))``); a
+    projection the model already holds packed is unpacked."""
     w = L[name]
     if isinstance(w, tuple):
         return ref.q4_dequant(*ref.q4_unpack(w[0], w[1])).float()
+    if not isinstance(w, torch.Tensor):  # ops.Mx4Weight
+        return ref.mx4_dequant(*ref.mx4_unpack(w.qw, w.qe)).float()
     if weight_dtype == "int4":
         return ref.q4_dequant(*ref.q4_quantize(w)).float()
+    if weight_dtype == "mxfp4":
+        return ref.mx4_dequant(*ref.mx4_quantize(w)).float()
     return w.float()
 
 
@@ -56,14 +61,15 @@ def dense_hidden(model, tokens, kv_cache_dtype: str | None = None, weight_dtype:
     head and the embedding pooling read.  ``kv_cache_dtype="fp8"``: the
     post-RoPE K and the V rows go through the fp8 KV cache's format per (token, kv head)
     (``ops.reference.fp8_fake_quant``), the oracle of an engine with that cache; None / "bf16":
-    no quantisation.  ``weight_dtype="int4"``: the fake-quant oracle of an int4-weights engine, the
-    qkv / o / gate_up / down weights of a dense model through ``ref.q4_quantize`` and back."""
+    no quantisation.  ``weight_dtype="int4"`` / ``"mxfp4"``: the fake-quant oracle of an engine with
+    those weights, the qkv / o / gate_up / down weights of a dense model through ``ref.q4_quantize``
+    / ``ref.mx4_quantize`` and back."""
     if kv_cache_dtype not in (None, "bf16", "fp8"):
         raise ValueError(f"kv_cache_dtype {kv_cache_dtype!r}")
-    if weight_dtype not in (None, "bf16", "int4"):
+    if weight_dtype not in (None, "bf16", "int4", "mxfp4"):
         raise ValueError(f"weight_dtype {weight_dtype!r}")
-    if weight_dtype == "int4" and model.cfg.is_moe:
-        raise ValueError('weight_dtype="int4" is not supported for MoE models')
+    if weight_dtype in ("int4", "mxfp4") and model.cfg.is_moe:
+        raise ValueError(f'weight_dtype="{weight_dtype}" is not supported for MoE models')
     cfg = model.cfg
     dev = model.embed.device
     T = len(tokens)

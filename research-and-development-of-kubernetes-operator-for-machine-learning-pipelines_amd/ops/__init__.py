@@ -824,6 +824,77 @@ def gemm_q4(x: torch.Tensor, W, epi: int = EPI_NONE) -> torch.Tensor:
     return y.view(*lead, -1)
 
 
+# -------------------------------------------------------- mxfp4 weights --
+# W4A16 in OCP MXFP4 (csrc/gemm_mx4.hip; the format is ref.mx4_quantize's).  The same two routes as
+# int4: the weight-streaming kernel up to MX4_WS_MAX_M rows, above it the dequantiser into the
+# scratch of ``q4_reserve_scratch`` and the unchanged ``gemm``.
+MX4_WS_KERNEL_MAX_M = 64  # gemm_mx4_kernel's MT limit (4 row tiles of 16)
+MX4_WS_MAX_M = min(MX4_WS_KERNEL_MAX_M, max(0, int(os.environ.get("MLOP_MX4_WS_MAX_M", "64"))))
+
+
+class Mx4Weight:
+    """A packed MXFP4 projection: ``qw`` / ``qe`` of ``ref.mx4_pack`` and the logical [N, K].  A class
+    of its own (an int4 projection is a plain tuple) so that the two packed forms can be told apart."""
+    __slots__ = ("qw", "qe", "N", "K")
+
+    def __init__(self, qw: torch.Tensor, qe: torch.Tensor, N: int, K: int):
+        self.qw, self.qe, self.N, self.K = qw, qe, N, K
+
+
+def mx4_pack(codes: torch.Tensor, e: torch.Tensor) -> Mx4Weight:
+    """(codes uint8 [N, K], e uint8 [N, K / 32]) -> the kernel's layout."""
+    return Mx4Weight(*ref.mx4_pack(codes, e), int(codes.shape[0]), int(codes.shape[1]))
+
+
+def mx4_quantize_pack(w: torch.Tensor) -> Mx4Weight:
+    """bf16 [N, K] -> packed W (ref.mx4_quantize, then the layout), on w's device."""
+    return mx4_pack(*ref.mx4_quantize(w))
+
+
+def mx4_bytes(N: int, K: int) -> int:
+    """Bytes of a packed [N, K] projection: nibbles + one scale byte per 32."""
+    return N * K // 2 + N * K // 32
+
+
+def mx4_dequant(W: Mx4Weight, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Packed W -> bf16 [N, K] row-major, bit-equal to ``ref.mx4_dequant``."""
+    if not W.qw.is_cuda:
+        y = ref.mx4_dequant(*ref.mx4_unpack(W.qw, W.qe))
+        if out is not None:
+            out.copy_(y)
+            return out
+        return y
+    _need_gpu()
+    out = torch.empty(W.N, W.K, dtype=torch.bfloat16, device=W.qw.device) if out is None else out
+    torch.ops.mlop.mx4_dequant(out, W.qw, W.qe)
+    return out
+
+
+def gemm_mx4(x: torch.Tensor, W: Mx4Weight, epi: int = EPI_NONE) -> torch.Tensor:
+    """y = epi(x @ dequant(W)^T) for a packed MXFP4 W.  M <= MX4_WS_MAX_M: gemm_mx4.hip (the scaled
+    weights are exact bf16 MFMA operands, fp32 accumulation; ``ref.gemm_mx4``), SiLU-mul as the
+    separate interleaved kernel.  Larger M: dequantise, then ``gemm(x, scratch, epi)``."""
+    N, K = W.N, W.K
+    if x.shape[-1] != K:
+        raise ValueError(f"gemm_mx4: x has {x.shape[-1]} columns, the weight K = {K}")
+    lead = x.shape[:-1]
+    x2 = x.reshape(-1, K)
+    if not x.is_cuda:
+        return gemm(x2, mx4_dequant(W), epi=epi).view(*lead, -1)
+    M = x2.shape[0]
+    if M > MX4_WS_MAX_M or M == 0:
+        wd = mx4_dequant(W, q4_reserve_scratch(x.device, N * K)[: N * K].view(N, K))
+        return gemm(x2, wd, epi=epi).view(*lead, -1)
+    _need_gpu()
+    if x2.stride(-1) != 1 or x2.stride(0) % 8:
+        x2 = x2.contiguous()
+    y = torch.empty(M, N, dtype=x.dtype, device=x.device)
+    torch.ops.mlop.gemm_mx4(y, x2, W.qw, W.qe, N)
+    if epi == EPI_SILU_MUL:
+        y = silu_mul(y, interleaved=True)
+    return y.view(*lead, -1)
+
+
 def argmax(logits: torch.Tensor) -> torch.Tensor:
     if not logits.is_cuda:
         return logits.argmax(-1)

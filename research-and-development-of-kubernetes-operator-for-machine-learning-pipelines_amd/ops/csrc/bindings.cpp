@@ -679,6 +679,44 @@ void q4_dequant(Tensor out, Tensor qw, Tensor qs) {
               "q4_dequant: shape refused");
 }
 
+// MXFP4 weights (gemm_mx4.hip): qw int32 [N / 16, K / 128, 64, 4] + qe int32 [N / 16, K / 128, 16] (ops.mx4_pack)
+static void check_mx4(const Tensor& qw, const Tensor& qe, int64_t N, int64_t K) {
+  TORCH_CHECK(N >= 16 && N % 16 == 0 && K >= 128 && K % 128 == 0, "mxfp4 weights need N % 16 == 0 and K % 128 == 0, not N = ",
+              N, ", K = ", K);
+  TORCH_CHECK(qw.is_cuda() && qw.scalar_type() == at::kInt && qw.is_contiguous() && qw.numel() == N * K / 8,
+              "qw must be int32 [N / 16, K / 128, 64, 4] on the GPU");
+  check_i32(qe, "qe");
+  TORCH_CHECK(qe.is_contiguous() && qe.numel() == N * K / 128, "qe must be int32 [N / 16, K / 128, 16]");
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(qw.data_ptr()) & 15) == 0, "qw must be 16-B aligned");
+}
+
+void gemm_mx4(Tensor out, Tensor a, Tensor qw, Tensor qe, int64_t N, int64_t rb) {
+  check_a(a);
+  const int64_t M = a.size(0), K = a.size(1);
+  check_mx4(qw, qe, N, K);
+  TORCH_CHECK(M >= 1 && M <= 64, "gemm_mx4: 1 <= M <= 64 (ops.gemm_mx4 dequantises above), not ", M);
+  TORCH_CHECK(out.is_cuda() && out.scalar_type() == at::kBFloat16 && out.dim() == 2 && out.size(0) == M &&
+                  out.size(1) == N && out.stride(1) == 1 && out.device() == a.device() && qw.device() == a.device() &&
+                  qe.device() == a.device(), "gemm_mx4: out bf16 [M, N] on a's device");
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(a.data_ptr()) & 15) == 0, "a must be 16-B aligned");
+  c10::DeviceGuard g(a.device());
+  TORCH_CHECK(mlop::launch_gemm_mx4(a.data_ptr(), (int)a.stride(0), qw.data_ptr(), qe.data_ptr(), out.data_ptr(),
+                                    (int)out.stride(0), (int)M, (int)N, (int)K, (int)rb, cur_stream()),
+              "gemm_mx4: shape or rb refused");
+}
+
+void mx4_dequant(Tensor out, Tensor qw, Tensor qe) {
+  check_bf16(out, "out");
+  TORCH_CHECK(out.dim() == 2, "mx4_dequant: out bf16 [N, K]");
+  const int64_t N = out.size(0), K = out.size(1);
+  check_mx4(qw, qe, N, K);
+  TORCH_CHECK(qw.device() == out.device() && qe.device() == out.device(), "mx4_dequant: one device");
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(out.data_ptr()) & 15) == 0, "out must be 16-B aligned");
+  c10::DeviceGuard g(out.device());
+  TORCH_CHECK(mlop::launch_mx4_dequant(out.data_ptr(), qw.data_ptr(), qe.data_ptr(), (int)N, (int)K, cur_stream()),
+              "mx4_dequant: shape refused");
+}
+
 void gemm_ws_plan(int64_t rb, int64_t u, int64_t nt) { mlop::gemm_ws_plan((int)rb, (int)u, (int)nt); }
 
 // grouped (MoE): rows of a sorted by group, offsets [G+1]; w [G, N, K]
@@ -1385,6 +1423,8 @@ TORCH_LIBRARY(mlop, m) {
   m.def("gemm_ws(Tensor(a!) out, Tensor a, Tensor w, int epi, bool rs, float eps) -> bool");
   m.def("gemm_q4(Tensor(a!) out, Tensor a, Tensor qw, Tensor qs, int N, int rb=0) -> ()");
   m.def("q4_dequant(Tensor(a!) out, Tensor qw, Tensor qs) -> ()");
+  m.def("gemm_mx4(Tensor(a!) out, Tensor a, Tensor qw, Tensor qe, int N, int rb=0) -> ()");
+  m.def("mx4_dequant(Tensor(a!) out, Tensor qw, Tensor qe) -> ()");
   m.def("flash_prefill(Tensor(a!) out, Tensor q, Tensor k_cache, Tensor v_cache, Tensor block_tables, "
         "Tensor ptile_seq, Tensor ptile_q0, Tensor q_start, Tensor q_len, Tensor ctx_len, float scale, "
         "int window=0) -> ()");
@@ -1423,6 +1463,8 @@ TORCH_LIBRARY_IMPL(mlop, CUDA, m) {
   m.impl("gemm_ws", &gemm_ws);
   m.impl("gemm_q4", &gemm_q4);
   m.impl("q4_dequant", &q4_dequant);
+  m.impl("gemm_mx4", &gemm_mx4);
+  m.impl("mx4_dequant", &mx4_dequant);
   m.impl("grouped_gemm", &grouped_gemm);
   m.impl("gemm_add_rmsnorm", &gemm_add_rmsnorm);
   m.impl("gemm_res_ss", &gemm_res_ss);

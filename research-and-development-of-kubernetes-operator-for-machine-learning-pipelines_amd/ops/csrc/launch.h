@@ -146,6 +146,12 @@ void launch_ws(const void* A, int lda, const void* B, int ldb, void* C, int ldc,
 bool launch_gemm_q4(const void* A, int lda, const void* qw, const void* qs, void* C, int ldc, int M, int N, int K,
                     int rb, hipStream_t st);
 bool launch_q4_dequant(void* out, const void* qw, const void* qs, int N, int K, hipStream_t st);
+// MXFP4 weights (gemm_mx4.hip): qw uint32 [N / 16, K / 128, 64, 4] + qe uint32 [N / 16, K / 128, 16]
+// (ops.mx4_pack: e2m1 codes in nibble order, four e8m0 scale bytes per row and tile).  The same
+// contract as the int4 pair above
+bool launch_gemm_mx4(const void* A, int lda, const void* qw, const void* qe, void* C, int ldc, int M, int N, int K,
+                     int rb, hipStream_t st);
+bool launch_mx4_dequant(void* out, const void* qw, const void* qe, int N, int K, hipStream_t st);
 void launch_gemv_rs(const void* A, int lda, const void* B, void* C, int ldc, int M, int N, int K, int epi,
                     const RopeEpi& re, float eps, hipStream_t st);
 void launch_gemv_res(const void* A, int lda, const void* B, void* residual, int M, int N, int K, hipStream_t st);

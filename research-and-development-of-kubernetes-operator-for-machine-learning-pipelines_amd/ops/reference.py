@@ -260,6 +260,94 @@ def q4_unpack(qw: torch.Tensor, qs: torch.Tensor):
     return q, qs.permute(0, 2, 1).reshape(NB * 16, G).contiguous()
 
 
+# -------------------------------------------------------- mxfp4 weights --
+# W4A16, OCP microscaling: e2m1 codes (uint8 0..15: bit 3 the sign, bits 0-2 an index into MX4_GRID)
+# and one e8m0 scale byte e per (weight row, 32 consecutive k), meaning 2^(e - 127).  Every
+# dequantised value 2^(e - 127) * grid is a normal bf16 for e in [2, 252]: nothing rounds anywhere.
+# (mx4_quantize yields no e above 252 from finite bf16 input; at 253 / 254 the codes for 4 and 6 /
+# 2 .. 6 would leave bf16's range, so those two bytes are outside the format.)
+MX4_GROUP = 32
+MX4_TILE_K = 128  # the device layout's tile: four groups = four MFMA K-steps
+MX4_GRID = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+# the grid's midpoints; a tie goes to the even code, so the upper neighbour takes it where it is even
+_MX4_MID = ((0.25, False), (0.75, True), (1.25, False), (1.75, True), (2.5, False), (3.5, True), (5.0, False))
+
+
+def _mx4_check(N: int, K: int) -> None:
+    if N < 16 or N % 16 or K < MX4_TILE_K or K % MX4_TILE_K:
+        raise ValueError(f"mxfp4 weights need N % 16 == 0 and K % {MX4_TILE_K} == 0, not [N = {N}, K = {K}]")
+
+
+def _mx4_scale(e: torch.Tensor) -> torch.Tensor:
+    """fp32 2^(e - 127) from the scale bytes, by its bits (1 <= e <= 254)."""
+    return (e.to(torch.int32) << 23).view(torch.float32)
+
+
+def mx4_quantize(w: torch.Tensor):
+    """w bf16 [N, K] -> (codes uint8 [N, K], e uint8 [N, K / 32]).  Per group e = floor(log2(amax))
+    - 2 + 127 clamped to [2, 254] (127 for an all-zero group), v = w / 2^(e - 127) exactly in fp32,
+    rounded to the nearest grid value with ties to the even code and saturated at 6.  A value that
+    rounds to zero gets code 0 whatever its sign."""
+    N, K = w.shape
+    _mx4_check(N, K)
+    wg = w.float().view(N, K // MX4_GROUP, MX4_GROUP)
+    amax = wg.abs().amax(-1)
+    _, ex = torch.frexp(amax)                                       # amax = m 2^ex, m in [0.5, 1)
+    e = torch.where(amax > 0, (ex + 124).clamp(2, 254), torch.full_like(ex, 127))
+    v = wg / _mx4_scale(e)[..., None]
+    a = v.abs()
+    idx = torch.zeros_like(a, dtype=torch.int32)
+    for mid, up in _MX4_MID:
+        idx += (a >= mid) if up else (a > mid)
+    codes = idx + 8 * ((v < 0) & (idx > 0))
+    return codes.to(torch.uint8).view(N, K), e.to(torch.uint8)
+
+
+def mx4_dequant(codes: torch.Tensor, e: torch.Tensor) -> torch.Tensor:
+    """bf16 [N, K]: (-1)^bit3 * MX4_GRID[bits 0-2] * 2^(e - 127), exact."""
+    grid = torch.tensor(MX4_GRID, dtype=torch.float32, device=codes.device)
+    c = codes.to(torch.int64)
+    v = torch.where(c >= 8, -grid[c & 7], grid[c & 7])
+    return (v * _mx4_scale(e).repeat_interleave(MX4_GROUP, dim=1)).to(torch.bfloat16)
+
+
+def gemm_mx4(x: torch.Tensor, codes: torch.Tensor, e: torch.Tensor, dtype=torch.float64) -> torch.Tensor:
+    """x @ dequant^T in ``dtype``, unrounded."""
+    return x.to(dtype) @ mx4_dequant(codes, e).to(dtype).T
+
+
+def _wrap_i32(word: torch.Tensor) -> torch.Tensor:
+    return torch.where(word >= 2 ** 31, word - 2 ** 32, word).to(torch.int32)
+
+
+def mx4_pack(codes: torch.Tensor, e: torch.Tensor):
+    """The device layout of csrc/gemm_mx4.hip: (qw int32 [N / 16, K / 128, 64, 4], qe int32
+    [N / 16, K / 128, 16]).  Lane l's 4 words of tile (nb, g) hold weight row 16 nb + (l & 15); word
+    j the codes of k = 128 g + 32 j + 8 (l >> 4) + i, i = 0..7, code i at nibble i.  qe[nb, g, r]
+    holds the four scale bytes of row 16 nb + r in that tile, K-step j at byte j."""
+    N, K = codes.shape
+    _mx4_check(N, K)
+    G = K // MX4_TILE_K
+    u = codes.to(torch.int64).view(N // 16, 16, G, 4, 4, 8)          # nb, row, g, j, chunk (l >> 4), i
+    u = u.permute(0, 2, 4, 1, 3, 5)                                 # nb, g, chunk, row, j, i: lane = 16 chunk + row
+    word = (u << (4 * torch.arange(8, device=codes.device))).sum(-1)
+    qw = _wrap_i32(word).reshape(N // 16, G, 64, 4).contiguous()
+    b = e.to(torch.int64).view(N // 16, 16, G, 4).permute(0, 2, 1, 3)  # nb, g, row, j
+    qe = _wrap_i32((b << (8 * torch.arange(4, device=e.device))).sum(-1)).contiguous()
+    return qw, qe
+
+
+def mx4_unpack(qw: torch.Tensor, qe: torch.Tensor):
+    """The inverse of ``mx4_pack``: (codes uint8 [N, K], e uint8 [N, K / 32])."""
+    NB, G = qw.shape[0], qw.shape[1]
+    w = qw.to(torch.int64) & 0xFFFFFFFF
+    u = (w[..., None] >> (4 * torch.arange(8, device=qw.device))) & 15  # nb, g, lane, j, i
+    u = u.view(NB, G, 4, 16, 4, 8).permute(0, 3, 1, 4, 2, 5)        # nb, row, g, j, chunk, i
+    b = ((qe.to(torch.int64) & 0xFFFFFFFF)[..., None] >> (8 * torch.arange(4, device=qe.device))) & 255
+    e = b.permute(0, 2, 1, 3).reshape(NB * 16, G * 4)               # nb, row, g, j
+    return u.to(torch.uint8).reshape(NB * 16, G * MX4_TILE_K), e.to(torch.uint8)
+
+
 # ------------------------------------------------------------------ MoE --
 
 def moe_route(logits, top_k, renorm=True):

@@ -25,10 +25,10 @@ def build_engine(model: str = "llama3-8b", device="cuda", seed: int = 0, tp_stat
     t0 = time.perf_counter()
     ckpt = resolve_model_dir(model_uri)
     if ckpt is not None:
-        # int4 weights: the norms are not folded into qkv / gate_up (the quantised forward applies
-        # them itself; a fold would only change what gets quantised)
+        # int4 / mxfp4 weights: the norms are not folded into qkv / gate_up (the quantised forward
+        # applies them itself; a fold would only change what gets quantised)
         m = load_pretrained(ckpt, device=device, dtype=dtype, pstate=tp_state,
-                            fold_norms=engine_kwargs.get("weight_dtype", "bf16") != "int4")
+                            fold_norms=engine_kwargs.get("weight_dtype", "bf16") == "bf16")
     else:
         m = build_model(model, device=device, dtype=dtype, pstate=tp_state, seed=seed)
     if torch.device(device).type == "cuda":

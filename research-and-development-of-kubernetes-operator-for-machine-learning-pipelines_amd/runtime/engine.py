@@ -261,8 +261,10 @@ class EngineConfig:
     kv_cache_dtype: str = "bf16"
     # element type of the qkv / o / gate_up / down weights: "bf16", or "int4" = symmetric 4-bit
     # values with one bf16 scale per (row, 128 columns) (ops/reference.py "int4 weights"), quantised
-    # on the device once the weights are loaded: 3.9x fewer projection bytes.  Dense TP = 1 models
-    # without LoRA; embedding, LM head and norms stay bf16.  "bf16" changes no launch or allocation.
+    # on the device once the weights are loaded: 3.9x fewer projection bytes; or "mxfp4" = OCP
+    # microscaling e2m1 values with one e8m0 power-of-two scale per (row, 32 columns) ("mxfp4
+    # weights" there): 3.8x fewer.  Dense TP = 1 models without LoRA; embedding, LM head and norms
+    # stay bf16.  "bf16" changes no launch or allocation.
     weight_dtype: str = "bf16"
     # speculative decoding by prompt lookup (runtime/spec.py): up to ``spec_tokens`` (k <= 7) draft
     # tokens per row, found by matching the sequence's last ``spec_ngram_max`` .. ``spec_ngram_min``
@@ -418,14 +420,16 @@ class Engine:
                 raise ValueError('kv_cache_dtype="fp8" is not supported for MoE models / expert parallelism')
             if mc.head_dim != 128:
                 raise ValueError('kv_cache_dtype="fp8" needs head_dim 128')
-        if weight_dtype_check(cfg.weight_dtype) == "int4":  # ValueError for an unknown name
+        wd = weight_dtype_check(cfg.weight_dtype)  # ValueError for an unknown name
+        if wd != "bf16":
             if model.ps.tp.size > 1:
-                raise ValueError('weight_dtype="int4" needs tensor parallel size 1')
+                raise ValueError(f'weight_dtype="{wd}" needs tensor parallel size 1')
             if getattr(mc, "is_moe", False) or model.ps.ep.size > 1:
-                raise ValueError('weight_dtype="int4" is not supported for MoE models / expert parallelism')
+                raise ValueError(f'weight_dtype="{wd}" is not supported for MoE models / expert parallelism')
             if cfg.max_adapters > 0:
-                raise ValueError('weight_dtype="int4" does not serve LoRA adapters (max_adapters must be 0)')
-            model.quantize_int4()  # before anything below sizes itself from the free memory
+                raise ValueError(f'weight_dtype="{wd}" does not serve LoRA adapters (max_adapters must be 0)')
+            # before anything below sizes itself from the free memory
+            (model.quantize_int4 if wd == "int4" else model.quantize_mxfp4)()
         self.spec_k = int(cfg.spec_tokens or 0)
         # optional callable (seq, cap) -> list[int]: replaces the device n-gram proposals (the
         # extension point of a draft-model proposer; lets tests force any acceptance pattern)

@@ -79,7 +79,7 @@ class RuntimeMetrics:
         # info-style: constant 1, the engine's kv_cache_dtype ("bf16" / "fp8") as the label
         self.kv_dtype = Gauge("mlop_kv_cache_dtype_info", "KV cache element type of the engine (label dtype)",
                               base + ["dtype"], registry=r)
-        # likewise the engine's weight_dtype ("bf16" / "int4")
+        # likewise the engine's weight_dtype ("bf16" / "int4" / "mxfp4")
         self.weight_dtype = Gauge("mlop_weight_dtype_info", "Projection weight element type of the engine (label dtype)",
                                   base + ["dtype"], registry=r)
         self.ready = Gauge("mlop_ready", "1 when the model is loaded and graphs captured", base, registry=r)
