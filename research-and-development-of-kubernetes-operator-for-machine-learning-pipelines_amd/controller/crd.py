@@ -88,6 +88,7 @@ class CanaryPolicy:
 
 KV_CACHE_DTYPES = ("bf16", "fp8")  # spec.kvCacheDtype (manifests/crd.yaml's enum)
 WEIGHT_DTYPES = ("bf16", "int4", "mxfp4")  # spec.weightDtype (manifests/crd.yaml's enum)
+EXPERT_WEIGHT_DTYPES = ("bf16", "mxfp4")  # spec.expertWeightDtype (manifests/crd.yaml's enum)
 MAX_SPECULATIVE_TOKENS = 7         # spec.speculativeTokens (manifests/crd.yaml's maximum; runtime/spec.py)
 MAX_GUIDED_STATES = 32767          # spec.guidedDecodingStates (int16 arena entries; runtime/guided.py)
 MAX_EMBEDDING_SLOTS = 4096         # spec.embeddingSlots (manifests/crd.yaml's maximum; EngineConfig.embed_slots)
@@ -115,6 +116,8 @@ class ModelSpec:
     # projection weights of the LLM runtime: None / "bf16", "int4" (group-128 symmetric) or "mxfp4"
     # (e2m1 + one e8m0 scale per 32), both quantised at load
     weight_dtype: str | None = None
+    # expert matrices of a MoE model in the LLM runtime: None / "bf16", or "mxfp4" (quantised at load)
+    expert_weight_dtype: str | None = None
     # draft tokens per step of the LLM runtime's prompt-lookup speculative decoding: None / 0 = off, 1..7
     speculative_tokens: int | None = None
     # rows of the LLM runtime's guided-decoding grammar arena: None / 0 = off, up to 32767
@@ -139,6 +142,7 @@ class ModelSpec:
                                   if isinstance(a, dict)),
                    kv_cache_dtype=spec.get("kvCacheDtype"),
                    weight_dtype=spec.get("weightDtype"),
+                   expert_weight_dtype=spec.get("expertWeightDtype"),
                    speculative_tokens=spec.get("speculativeTokens"),
                    guided_decoding_states=spec.get("guidedDecodingStates"),
                    embedding_slots=spec.get("embeddingSlots"))
@@ -174,6 +178,18 @@ class ModelSpec:
                                 "expertParallel = 1 (dense models on one GPU)")
                 if self.adapters:
                     errs.append(f"spec.weightDtype {self.weight_dtype} is not supported with adapters")
+        if self.expert_weight_dtype is not None:
+            if self.expert_weight_dtype not in EXPERT_WEIGHT_DTYPES:
+                errs.append(f"spec.expertWeightDtype must be one of {list(EXPERT_WEIGHT_DTYPES)}, "
+                            f"not {self.expert_weight_dtype!r}")
+            elif self.expert_weight_dtype != "bf16":
+                if int(self.tensor_parallel or 1) > 1 or int(self.expert_parallel or 1) > 1:
+                    errs.append(f"spec.expertWeightDtype {self.expert_weight_dtype} needs tensorParallel = 1 and "
+                                "expertParallel = 1 (MoE models on one GPU)")
+                if (self.weight_dtype or "bf16") != "bf16":
+                    errs.append(f"spec.expertWeightDtype {self.expert_weight_dtype} needs weightDtype bf16")
+                if self.adapters:
+                    errs.append(f"spec.expertWeightDtype {self.expert_weight_dtype} is not supported with adapters")
         k = self.speculative_tokens
         if k is not None:
             if isinstance(k, bool) or not isinstance(k, int) or not 0 <= k <= MAX_SPECULATIVE_TOKENS:

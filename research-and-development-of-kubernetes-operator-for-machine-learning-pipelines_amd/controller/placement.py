@@ -48,7 +48,7 @@ def plan(arch: str | ModelConfig, max_model_len: int = 4096, max_num_seqs: int =
          reserve_gb: float = 8.0, requested_tp: int | None = None, requested_ep: int | None = None,
          kv_target_fraction: float = 0.5, free_gpus: int | None = None,
          kv_cache_dtype: str | None = None, grammar_states: int = 0,
-         weight_dtype: str | None = None) -> Placement:
+         weight_dtype: str | None = None, expert_weight_dtype: str | None = None) -> Placement:
     """``free_gpus``: GPUs the target node still has unallocated (reconciler.node_capacity);
     a placement needing more is returned with ``fits=False`` and the reason (the pod would
     stay Pending), whatever its HBM arithmetic says.  ``kv_cache_dtype`` ("bf16" / "fp8"): the
@@ -56,9 +56,13 @@ def plan(arch: str | ModelConfig, max_model_len: int = 4096, max_num_seqs: int =
     included (None: bf16).  ``grammar_states``: rows of the guided-decoding arena (int16
     [states, vocab]), charged states x vocab x 2 bytes beside the weights.  ``weight_dtype``
     ("bf16" / "int4" / "mxfp4"): 4-bit weights (``ModelConfig.weight_bytes(weight_dtype=)``: packed projections,
-    scales and the dequantisation scratch) are planned on one GPU only; they are not sharded."""
+    scales and the dequantisation scratch) are planned on one GPU only; they are not sharded.
+    ``expert_weight_dtype`` ("bf16" / "mxfp4"): a MoE model's experts packed
+    (``ModelConfig.weight_bytes(expert_weight_dtype=)``: packed w13 / w2 plus the scratch), likewise
+    on one GPU only."""
     p = _plan(arch, max_model_len, max_num_seqs, hbm_gb, gpus_per_node, utilization, reserve_gb,
-              requested_tp, requested_ep, kv_target_fraction, kv_cache_dtype, grammar_states, weight_dtype)
+              requested_tp, requested_ep, kv_target_fraction, kv_cache_dtype, grammar_states, weight_dtype,
+              expert_weight_dtype)
     if free_gpus is not None and p.gpus > free_gpus:
         p.fits = False
         p.reason = (f"needs {p.gpus} GPUs (TP={p.tensorParallel}), the node has {free_gpus} of "
@@ -67,11 +71,15 @@ def plan(arch: str | ModelConfig, max_model_len: int = 4096, max_num_seqs: int =
 
 
 def _plan(arch, max_model_len, max_num_seqs, hbm_gb, gpus_per_node, utilization, reserve_gb, requested_tp,
-          requested_ep, kv_target_fraction, kv_cache_dtype=None, grammar_states=0, weight_dtype=None) -> Placement:
+          requested_ep, kv_target_fraction, kv_cache_dtype=None, grammar_states=0, weight_dtype=None,
+          expert_weight_dtype=None) -> Placement:
     cfg = arch if isinstance(arch, ModelConfig) else get_config(arch)
     usable = hbm_gb * utilization
     w4 = weight_dtype in ("int4", "mxfp4")
-    wbytes = cfg.weight_bytes(weight_dtype=None if w4 and cfg.is_moe else weight_dtype)
+    x4 = expert_weight_dtype == "mxfp4"
+    x4_ok = x4 and cfg.is_moe and not w4  # the packed bytes are defined: charge them
+    wbytes = cfg.weight_bytes(weight_dtype=None if w4 and cfg.is_moe else weight_dtype,
+                              expert_weight_dtype="mxfp4" if x4_ok else None)
     kv_tok = cfg.kv_bytes_per_token(kv_cache_dtype=kv_cache_dtype or "bf16")
     kv_target = max_num_seqs * max_model_len * kv_tok * kv_target_fraction
     arena = int(grammar_states or 0) * cfg.vocab_size * 2  # guided decoding: int16 [states, vocab]
@@ -88,6 +96,12 @@ def _plan(arch, max_model_len, max_num_seqs, hbm_gb, gpus_per_node, utilization,
                          hbm_gb, fits, "" if fits else
                          f"needs {round((w + arena + kv_per_gpu) / GB + reserve_gb, 1)} GB/GPU > {round(usable, 1)}")
 
+    if x4:  # one GPU or nothing: the packed experts are not sharded
+        p = evaluate(1, 1)
+        if not x4_ok or int(requested_tp or 1) > 1 or int(requested_ep or 1) > 1:
+            p.fits, p.reason = False, (f"expertWeightDtype mxfp4 serves MoE models at tensorParallel = expertParallel "
+                                       f"= 1 with weightDtype bf16 ({cfg.name})")
+        return p
     if w4:  # one GPU or nothing: the packed projections are not sharded, MoE experts not quantised
         p = evaluate(1, 1)
         if cfg.is_moe or int(requested_tp or 1) > 1 or int(requested_ep or 1) > 1:

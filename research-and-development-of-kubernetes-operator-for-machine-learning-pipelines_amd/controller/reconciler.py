@@ -209,6 +209,7 @@ class MlflowModelReconciler:
                 # (appended only when set: CRs without the field keep the key their deployed predictors carry)
                 + (f"|kv={spec.kv_cache_dtype}" if spec.kv_cache_dtype else "")
                 + (f"|w={spec.weight_dtype}" if spec.weight_dtype else "")
+                + (f"|xw={spec.expert_weight_dtype}" if spec.expert_weight_dtype else "")
                 + (f"|gs={spec.guided_decoding_states}" if spec.guided_decoding_states else ""))
 
     async def desired_sd(self, body: dict, spec: ModelSpec, status: dict) -> dict | None:
@@ -262,7 +263,8 @@ class MlflowModelReconciler:
                              requested_tp=spec.tensor_parallel, requested_ep=spec.expert_parallel,
                              kv_target_fraction=spec.kv_target_fraction or 0.5,
                              free_gpus=node.get("free_gpus"), kv_cache_dtype=spec.kv_cache_dtype,
-                             weight_dtype=spec.weight_dtype, grammar_states=spec.guided_decoding_states or 0)
+                             weight_dtype=spec.weight_dtype, grammar_states=spec.guided_decoding_states or 0,
+                             expert_weight_dtype=spec.expert_weight_dtype)
                     placement = {"tensorParallel": p.tensorParallel, "expertParallel": p.expertParallel,
                                  "gpus": p.gpus, "weightGBPerGPU": p.weightGBPerGPU,
                                  "kvTokenCapacity": p.kvTokenCapacity, "fits": p.fits, "placementKey": key}
@@ -291,6 +293,8 @@ class MlflowModelReconciler:
                 engine_args["kv_cache_dtype"] = spec.kv_cache_dtype  # -> MLOP_ENGINE_KV_CACHE_DTYPE
             if spec.weight_dtype and runtime == seldon.RUNTIME_LLM:
                 engine_args["weight_dtype"] = spec.weight_dtype  # -> MLOP_ENGINE_WEIGHT_DTYPE
+            if spec.expert_weight_dtype and runtime == seldon.RUNTIME_LLM:
+                engine_args["expert_weight_dtype"] = spec.expert_weight_dtype  # -> MLOP_ENGINE_EXPERT_WEIGHT_DTYPE
             if spec.speculative_tokens and runtime == seldon.RUNTIME_LLM:
                 engine_args["spec_tokens"] = spec.speculative_tokens  # -> MLOP_ENGINE_SPEC_TOKENS
             if spec.guided_decoding_states and runtime == seldon.RUNTIME_LLM:

@@ -102,12 +102,23 @@ class ModelConfig:
         H, I = self.hidden_size, self.intermediate_size
         return ((self.q_size + 2 * self.kv_size, H), (H, self.q_size), (2 * I, H), (H, I))
 
-    def weight_bytes(self, dtype_bytes: int = 2, weight_dtype: str | None = None) -> int:
+    def weight_bytes(self, dtype_bytes: int = 2, weight_dtype: str | None = None,
+                     expert_weight_dtype: str | None = None) -> int:
         """Bytes of the weights.  ``weight_dtype="int4"`` (dense models): the four projections of
         every layer packed (N K / 2 nibble bytes + N K / 64 of bf16 group scales each), everything
         else at ``dtype_bytes``, plus the bf16 dequantisation scratch of the largest projection.
-        ``"mxfp4"``: likewise with N K / 2 + N K / 32 (one scale byte per 32) per projection."""
+        ``"mxfp4"``: likewise with N K / 2 + N K / 32 (one scale byte per 32) per projection.
+        ``expert_weight_dtype="mxfp4"`` (MoE models, ``weight_dtype`` bf16): every layer's w13 and w2
+        packed that way, plus the bf16 scratch of one layer's w13 (the larger of the two)."""
         weight_dtype_check(weight_dtype or "bf16")
+        if expert_weight_dtype not in (None, "bf16", "mxfp4"):
+            raise ValueError(f"expert_weight_dtype must be one of ['bf16', 'mxfp4'], not {expert_weight_dtype!r}")
+        if expert_weight_dtype == "mxfp4":
+            if not self.is_moe or weight_dtype not in (None, "bf16"):
+                raise ValueError('expert_weight_dtype="mxfp4" needs a MoE model with weight_dtype "bf16"')
+            experts = 3 * self.hidden_size * self.intermediate_size * self.num_experts  # w13 + w2 of a layer
+            rest = self.num_params() - self.num_layers * experts
+            return self.num_layers * (experts // 2 + experts // 32) + rest * dtype_bytes + 2 * (experts // 3 * 2)
         if weight_dtype not in ("int4", "mxfp4"):
             return self.num_params() * dtype_bytes
         if self.is_moe:

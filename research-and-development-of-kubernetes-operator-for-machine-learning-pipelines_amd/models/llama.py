@@ -166,7 +166,7 @@ class LlamaModel:
                     yield v
                 elif isinstance(v, tuple):  # a packed int4 projection (qw, qs, N, K)
                     yield from v[:2]
-                elif isinstance(v, ops.Mx4Weight):
+                elif isinstance(v, (ops.Mx4Weight, ops.Mx4Experts)):
                     yield from (v.qw, v.qe)
         yield self.final_norm
         if self.lm_head is not self.embed:

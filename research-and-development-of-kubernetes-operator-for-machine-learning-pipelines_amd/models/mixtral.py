@@ -19,6 +19,9 @@ from .llama import LlamaModel
 
 
 class MixtralModel(LlamaModel):
+    # "mxfp4" after quantize_experts_mxfp4(): every layer's w13 / w2 are ops.Mx4Experts
+    expert_weight_dtype = "bf16"
+
     def _init_mlp(self, w):
         cfg = self.cfg
         E, H, I = cfg.num_experts, cfg.hidden_size, cfg.intermediate_size
@@ -43,6 +46,35 @@ class MixtralModel(LlamaModel):
         L["router"].copy_(F["router"].to(self.device, self.dtype))
         L["w13"].copy_(F["w13"][e0:e0 + n].to(self.device, self.dtype))
         L["w2"].copy_(F["w2"][e0:e0 + n].to(self.device, self.dtype))
+
+    @torch.no_grad()
+    def quantize_experts_mxfp4(self) -> "MixtralModel":
+        """Replace every layer's w13 / w2 by their MXFP4 form (ops.mx4_experts_quantize_pack: each
+        expert through ref.mx4_quantize), one layer at a time, each bf16 tensor freed before the
+        next is quantised.  Attention projections, router, embedding, LM head and norms stay bf16,
+        so the layer keeps its fused QKV + RoPE and O paths; parallel.moe.local_experts sends the
+        packed experts through ops.grouped_gemm_mx4."""
+        if self.expert_weight_dtype == "mxfp4":
+            return self
+        cfg = self.cfg
+        if self.ps.tp_size > 1 or self.ps.ep.size > 1:
+            raise ValueError('expert_weight_dtype="mxfp4" needs tensor parallel size 1 and expert parallel size 1')
+        if cfg.hidden_size % 128 or cfg.intermediate_size % 128:
+            raise ValueError(f'expert_weight_dtype="mxfp4" needs hidden_size % 128 == 0 and intermediate_size % 128 '
+                             f'== 0, not {cfg.hidden_size} / {cfg.intermediate_size} ({cfg.name})')
+        largest = 0
+        for L in self.layers:
+            for name in ("w13", "w2"):
+                largest = max(largest, L[name].numel())
+                L[name] = ops.mx4_experts_quantize_pack(L[name])
+        # the large-batch route dequantises one layer's w13 or w2 at a time into this scratch;
+        # reserved here so that a graph capture never grows it
+        self.q4_scratch_numel = largest
+        ops.q4_reserve_scratch(self.device, largest)
+        if self.device.type == "cuda":  # hand the freed bf16 blocks back: the KV pool is sized from free HBM
+            torch.cuda.empty_cache()
+        self.expert_weight_dtype = "mxfp4"
+        return self
 
     def _folds(self):
         return (("in_norm", "qkv"),)  # post_norm feeds the router and the experts

@@ -29,7 +29,19 @@ def _proj(L, name, weight_dtype):
     return w.float()
 
 
-def _mlp(model, i, x, weight_dtype=None):
+def _experts(w, expert_weight_dtype):
+    """fp32 [E, N, K] weights of a layer's experts.  ``expert_weight_dtype="mxfp4"``: through
+    ``ref.mx4_quantize`` and back (row by row, so the stacked matrix quantises as each expert does);
+    experts the model already holds packed (ops.Mx4Experts) are unpacked."""
+    if not isinstance(w, torch.Tensor):
+        S = w.stacked()
+        return ref.mx4_dequant(*ref.mx4_unpack(S.qw, S.qe)).float().view(w.E, w.N, w.K)
+    if expert_weight_dtype == "mxfp4":
+        return ref.mx4_dequant(*ref.mx4_quantize(w.reshape(-1, w.shape[-1]))).float().view(w.shape)
+    return w.float()
+
+
+def _mlp(model, i, x, weight_dtype=None, expert_weight_dtype=None):
     L = model.layers[i]
     if model.cfg.is_moe:
         logits = F.linear(x, L["router"].float())
@@ -37,12 +49,13 @@ def _mlp(model, i, x, weight_dtype=None):
         if model.cfg.norm_topk_prob:
             w = w / w.sum(-1, keepdim=True)
         out = torch.zeros_like(x)
+        w13, w2 = _experts(L["w13"], expert_weight_dtype), _experts(L["w2"], expert_weight_dtype)
         for e in range(model.cfg.num_experts):
             rows, k = (idx == e).nonzero(as_tuple=True)
             if rows.numel() == 0:
                 continue
-            gu = F.linear(x[rows], deinterleave_rows(L["w13"][e]).float())
-            h = F.linear(ref.silu_mul(gu.to(model.dtype)).float(), L["w2"][e].float())
+            gu = F.linear(x[rows], deinterleave_rows(w13[e]))
+            h = F.linear(ref.silu_mul(gu.to(model.dtype)).float(), w2[e])
             out.index_add_(0, rows, h * w[rows, k, None])
         return out
     gu = F.linear(x, deinterleave_rows(_proj(L, "gate_up", weight_dtype))).to(model.dtype)
@@ -50,20 +63,29 @@ def _mlp(model, i, x, weight_dtype=None):
 
 
 @torch.no_grad()
-def dense_logits(model, tokens, kv_cache_dtype: str | None = None, weight_dtype: str | None = None) -> torch.Tensor:
+def dense_logits(model, tokens, kv_cache_dtype: str | None = None, weight_dtype: str | None = None,
+                 expert_weight_dtype: str | None = None) -> torch.Tensor:
     """[T, V] fp32 logits of a single sequence (TP=1 models only): the LM head over ``dense_hidden``."""
-    return F.linear(dense_hidden(model, tokens, kv_cache_dtype, weight_dtype), model.lm_head.float())
+    return F.linear(dense_hidden(model, tokens, kv_cache_dtype, weight_dtype, expert_weight_dtype),
+                    model.lm_head.float())
 
 
 @torch.no_grad()
-def dense_hidden(model, tokens, kv_cache_dtype: str | None = None, weight_dtype: str | None = None) -> torch.Tensor:
+def dense_hidden(model, tokens, kv_cache_dtype: str | None = None, weight_dtype: str | None = None,
+                 expert_weight_dtype: str | None = None) -> torch.Tensor:
     """[T, H] fp32 final-normed hidden states of a single sequence (TP=1 models only): what the LM
     head and the embedding pooling read.  ``kv_cache_dtype="fp8"``: the
     post-RoPE K and the V rows go through the fp8 KV cache's format per (token, kv head)
     (``ops.reference.fp8_fake_quant``), the oracle of an engine with that cache; None / "bf16":
     no quantisation.  ``weight_dtype="int4"`` / ``"mxfp4"``: the fake-quant oracle of an engine with
     those weights, the qkv / o / gate_up / down weights of a dense model through ``ref.q4_quantize``
-    / ``ref.mx4_quantize`` and back."""
+    / ``ref.mx4_quantize`` and back.  ``expert_weight_dtype="mxfp4"``: the fake-quant oracle of an
+    engine with MXFP4 experts, every expert's w13 / w2 of a MoE model through ``ref.mx4_quantize``
+    and back, everything else fp32."""
+    if expert_weight_dtype not in (None, "bf16", "mxfp4"):
+        raise ValueError(f"expert_weight_dtype {expert_weight_dtype!r}")
+    if expert_weight_dtype == "mxfp4" and not model.cfg.is_moe:
+        raise ValueError('expert_weight_dtype="mxfp4" needs a MoE model')
     if kv_cache_dtype not in (None, "bf16", "fp8"):
         raise ValueError(f"kv_cache_dtype {kv_cache_dtype!r}")
     if weight_dtype not in (None, "bf16", "int4", "mxfp4"):
@@ -103,7 +125,7 @@ def dense_hidden(model, tokens, kv_cache_dtype: str | None = None, weight_dtype:
         a = torch.einsum("hqk,khd->qhd", s.softmax(-1), v).reshape(T, -1)
         res = res + F.linear(a, _proj(L, "o", weight_dtype))
         x = ref.rmsnorm(res, L["post_norm"].float(), cfg.rms_eps)
-        res = res + _mlp(model, i, x, weight_dtype)
+        res = res + _mlp(model, i, x, weight_dtype, expert_weight_dtype)
         nxt = model.layers[i + 1]["in_norm"] if i + 1 < len(model.layers) else model.final_norm
         x = ref.rmsnorm(res, nxt.float(), cfg.rms_eps)
     return x

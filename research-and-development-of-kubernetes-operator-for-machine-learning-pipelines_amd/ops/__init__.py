@@ -895,6 +895,84 @@ def gemm_mx4(x: torch.Tensor, W: Mx4Weight, epi: int = EPI_NONE) -> torch.Tensor
     return y.view(*lead, -1)
 
 
+# ------------------------------------------------ mxfp4 expert weights --
+# The experts of a MoE layer in MXFP4 (csrc/moe_mx4.hip): ``Mx4Weight``'s layout with the expert
+# outermost.  The streaming kernel serves a launch whose experts average up to
+# MX4_MOE_MAX_AVG_ROWS rows (any single expert may hold more: it is walked in 64-row chunks);
+# above, the layer's experts are dequantised into the scratch of ``q4_reserve_scratch`` and the
+# unchanged ``grouped_gemm`` runs.
+MX4_MOE_MAX_AVG_ROWS = max(0, int(os.environ.get("MLOP_MX4_MOE_MAX_AVG_ROWS", "256")))
+
+
+class Mx4Experts:
+    """Packed MXFP4 experts: ``qw`` int32 [E, N / 16, K / 128, 64, 4], ``qe`` int32 [E, N / 16, K / 128, 16]
+    and the logical [E, N, K].  Viewed as [E N / 16, ...] they are ``ref.mx4_pack`` of the stacked
+    [E N, K] matrix."""
+    __slots__ = ("qw", "qe", "E", "N", "K")
+
+    def __init__(self, qw: torch.Tensor, qe: torch.Tensor, E: int, N: int, K: int):
+        self.qw, self.qe, self.E, self.N, self.K = qw, qe, E, N, K
+
+    def stacked(self) -> Mx4Weight:
+        """The same bytes as the packed [E N, K] projection."""
+        return Mx4Weight(self.qw.view(-1, *self.qw.shape[2:]), self.qe.view(-1, *self.qe.shape[2:]),
+                         self.E * self.N, self.K)
+
+
+def mx4_experts_pack(codes: torch.Tensor, e: torch.Tensor) -> Mx4Experts:
+    """(codes uint8 [E, N, K], e uint8 [E, N, K / 32]) -> the kernel's layout."""
+    E, N, K = codes.shape
+    if N % 16:
+        raise ValueError(f"mxfp4 weights need N % 16 == 0 and K % {ref.MX4_TILE_K} == 0, not [N = {N}, K = {K}]")
+    qw, qe = ref.mx4_pack(codes.reshape(E * N, K), e.reshape(E * N, -1))
+    return Mx4Experts(qw.view(E, N // 16, *qw.shape[1:]), qe.view(E, N // 16, *qe.shape[1:]), E, N, K)
+
+
+def mx4_experts_unpack(W: Mx4Experts):
+    """The inverse of ``mx4_experts_pack``."""
+    S = W.stacked()
+    codes, e = ref.mx4_unpack(S.qw, S.qe)
+    return codes.view(W.E, W.N, W.K), e.view(W.E, W.N, -1)
+
+
+def mx4_experts_quantize_pack(w: torch.Tensor) -> Mx4Experts:
+    """bf16 [E, N, K] -> packed experts, each expert through ``ref.mx4_quantize``, on w's device."""
+    E, N, K = w.shape
+    parts = [mx4_quantize_pack(w[i]) for i in range(E)]  # ValueError unless N % 16 == 0 and K % 128 == 0
+    return Mx4Experts(torch.stack([p.qw for p in parts]), torch.stack([p.qe for p in parts]), E, N, K)
+
+
+def mx4_experts_dequant(W: Mx4Experts, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Packed experts -> bf16 [E, N, K] (``mx4_dequant`` of the stacked matrix: one launch)."""
+    return mx4_dequant(W.stacked(), None if out is None else out.view(W.E * W.N, W.K)).view(W.E, W.N, W.K)
+
+
+def grouped_gemm_mx4(xp, W: Mx4Experts, offsets, epi: int = EPI_NONE, avg_rows: int | None = None, a_rows=None):
+    """``grouped_gemm`` over packed MXFP4 experts: the same rows, ``offsets`` / ``a_rows`` meaning,
+    output order and epilogues.  ``avg_rows`` <= MX4_MOE_MAX_AVG_ROWS: moe_mx4.hip in one launch.
+    Above: dequantise the layer's experts, then ``grouped_gemm``.  CPU tensors take the reference."""
+    E, N, K = W.E, W.N, W.K
+    if xp.shape[-1] != K or offsets.numel() != E + 1:
+        raise ValueError(f"grouped_gemm_mx4: x has {xp.shape[-1]} columns and offsets {offsets.numel()} entries; "
+                         f"the experts are [{E}, {N}, {K}]")
+    if not xp.is_cuda:
+        return grouped_gemm(xp, mx4_experts_dequant(W), offsets, epi=epi, avg_rows=avg_rows, a_rows=a_rows)
+    R = xp.shape[0] if a_rows is None else a_rows.numel()
+    rows = avg_rows if avg_rows is not None else max(1, R // E)
+    if rows > MX4_MOE_MAX_AVG_ROWS:
+        wd = mx4_experts_dequant(W, q4_reserve_scratch(xp.device, E * N * K)[: E * N * K])
+        return grouped_gemm(xp, wd, offsets, epi=epi, avg_rows=avg_rows, a_rows=a_rows)
+    _need_gpu()
+    if epi not in (EPI_NONE, EPI_SILU_MUL):
+        raise ValueError(f"grouped_gemm_mx4: epi {epi}")
+    if xp.stride(-1) != 1 or xp.stride(0) % 8:
+        xp = xp.contiguous()
+    out = torch.empty(R, N if epi == EPI_NONE else N // 2, dtype=xp.dtype, device=xp.device)
+    if R > 0:
+        torch.ops.mlop.grouped_gemm_mx4(out, xp, W.qw, W.qe, offsets, N, epi, 0, a_rows)
+    return out
+
+
 def argmax(logits: torch.Tensor) -> torch.Tensor:
     if not logits.is_cuda:
         return logits.argmax(-1)

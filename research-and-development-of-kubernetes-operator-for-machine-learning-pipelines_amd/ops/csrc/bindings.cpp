@@ -739,6 +739,39 @@ void grouped_gemm(Tensor out, Tensor a, Tensor w, Tensor offsets, int64_t max_ro
                             a_rows ? a_rows->data_ptr<int>() : nullptr);
 }
 
+// grouped over MXFP4 experts (moe_mx4.hip): qw / qe of ops.Mx4Experts, N the rows of one expert
+void grouped_gemm_mx4(Tensor out, Tensor a, Tensor qw, Tensor qe, Tensor offsets, int64_t N, int64_t epi,
+                      int64_t rb, std::optional<Tensor> a_rows) {
+  check_a(a);
+  check_bf16(out, "out"); check_i32(offsets, "offsets");
+  const int64_t R = out.size(0), K = a.size(1), E = offsets.numel() - 1;
+  TORCH_CHECK(E >= 1 && offsets.is_contiguous(), "offsets must be int32 [E + 1]");
+  check_mx4(qw, qe, E * N, K);
+  TORCH_CHECK(epi == 0 || (epi == 1 && N % 32 == 0), "grouped_gemm_mx4: epi 0, or 1 with N % 32 == 0");
+  TORCH_CHECK(out.dim() == 2 && out.is_contiguous() && out.size(1) == (epi == 0 ? N : N / 2),
+              "grouped_gemm_mx4: out bf16 [R, N] (epi 1: [R, N / 2]) contiguous");
+  TORCH_CHECK(out.device() == a.device() && qw.device() == a.device() && qe.device() == a.device() &&
+                  offsets.device() == a.device(), "grouped_gemm_mx4: one device");
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(a.data_ptr()) & 15) == 0, "a must be 16-B aligned");
+  if (a_rows) {  // the permuted rows are out's and a holds the token rows they name
+    check_i32(*a_rows, "a_rows");
+    TORCH_CHECK(a_rows->is_contiguous() && a_rows->numel() >= R && a_rows->device() == a.device(),
+                "a_rows [R]: every permuted row's token row");
+  } else {
+    TORCH_CHECK(a.size(0) >= R, "grouped_gemm_mx4: a [R, K]");
+  }
+  c10::DeviceGuard g(a.device());
+  TORCH_CHECK(mlop::launch_moe_mx4(a.data_ptr(), (int)a.stride(0), a_rows ? a_rows->data_ptr<int>() : nullptr,
+                                   qw.data_ptr(), qe.data_ptr(), offsets.data_ptr<int>(), out.data_ptr(),
+                                   (int)out.stride(0), (int)R, (int)E, (int)N, (int)K, (int)epi, (int)rb,
+                                   cur_stream()),
+              "grouped_gemm_mx4: shape or rb refused");
+}
+
+int64_t moe_mx4_rb(int64_t R, int64_t E, int64_t N, int64_t epi) {
+  return mlop::moe_mx4_rb((int)R, (int)E, (int)N, (int)epi);
+}
+
 void moe_route(Tensor topw, Tensor topi, Tensor logits) {
   check_bf16(logits, "router logits");
   TORCH_CHECK(logits.dim() == 2 && logits.size(1) <= 64, "router logits [T, E<=64]");
@@ -1425,6 +1458,9 @@ TORCH_LIBRARY(mlop, m) {
   m.def("q4_dequant(Tensor(a!) out, Tensor qw, Tensor qs) -> ()");
   m.def("gemm_mx4(Tensor(a!) out, Tensor a, Tensor qw, Tensor qe, int N, int rb=0) -> ()");
   m.def("mx4_dequant(Tensor(a!) out, Tensor qw, Tensor qe) -> ()");
+  m.def("grouped_gemm_mx4(Tensor(a!) out, Tensor a, Tensor qw, Tensor qe, Tensor offsets, int N, int epi, int rb=0, "
+        "Tensor? a_rows=None) -> ()");
+  m.def("moe_mx4_rb(int R, int E, int N, int epi) -> int", &moe_mx4_rb);
   m.def("flash_prefill(Tensor(a!) out, Tensor q, Tensor k_cache, Tensor v_cache, Tensor block_tables, "
         "Tensor ptile_seq, Tensor ptile_q0, Tensor q_start, Tensor q_len, Tensor ctx_len, float scale, "
         "int window=0) -> ()");
@@ -1465,6 +1501,7 @@ TORCH_LIBRARY_IMPL(mlop, CUDA, m) {
   m.impl("q4_dequant", &q4_dequant);
   m.impl("gemm_mx4", &gemm_mx4);
   m.impl("mx4_dequant", &mx4_dequant);
+  m.impl("grouped_gemm_mx4", &grouped_gemm_mx4);
   m.impl("grouped_gemm", &grouped_gemm);
   m.impl("gemm_add_rmsnorm", &gemm_add_rmsnorm);
   m.impl("gemm_res_ss", &gemm_res_ss);

@@ -152,6 +152,14 @@ bool launch_q4_dequant(void* out, const void* qw, const void* qs, int N, int K, 
 bool launch_gemm_mx4(const void* A, int lda, const void* qw, const void* qe, void* C, int ldc, int M, int N, int K,
                      int rb, hipStream_t st);
 bool launch_mx4_dequant(void* out, const void* qw, const void* qe, int N, int K, hipStream_t st);
+// MXFP4 expert weights (moe_mx4.hip): the pair above with the expert outermost (qw [E, N / 16, ...]).
+// Rows offsets[e] .. offsets[e + 1] of the R permuted rows belong to expert e (device int32 [E + 1]);
+// a_rows (or null): permuted row r is row a_rows[r] of A.  epi 0: C [R, N]; 1: SiLU-mul of the
+// gate / up interleaved columns, C [R, N / 2] (N % 32 == 0).  rb 0 = moe_mx4_rb's rule, else 1 / 2 / 4
+// (2 / 4 under epi 1).  false: a shape or rb the kernel does not take (nothing launched)
+int moe_mx4_rb(int R, int E, int N, int epi);
+bool launch_moe_mx4(const void* A, int lda, const int* a_rows, const void* qw, const void* qe, const int* offsets,
+                    void* C, int ldc, int R, int E, int N, int K, int epi, int rb, hipStream_t st);
 void launch_gemv_rs(const void* A, int lda, const void* B, void* C, int ldc, int M, int N, int K, int epi,
                     const RopeEpi& re, float eps, hipStream_t st);
 void launch_gemv_res(const void* A, int lda, const void* B, void* residual, int M, int N, int K, hipStream_t st);

@@ -57,6 +57,12 @@ def local_experts(x, topw, topi, w13, w2, e0: int, n_local: int, dispatched=None
     else:
         xp, offsets, inv = dispatched
     avg = max(1, (T * k) // max(1, n_local))
+    if isinstance(w13, ops.Mx4Experts):  # MXFP4 experts (moe_mx4.hip); the tail is the plain combine's
+        a = ops.grouped_gemm_mx4(xp, w13, offsets, epi=ops.EPI_SILU_MUL, avg_rows=avg, a_rows=arow)
+        y = ops.grouped_gemm_mx4(a, w2, offsets, avg_rows=avg)
+        if isinstance(combine, tuple):
+            return ops.moe_combine_add_rmsnorm(y, inv, topw, *combine)
+        return ops.moe_combine(y, inv, topw) if combine else (y, inv)
     a = ops.grouped_gemm(xp, w13, offsets, epi=ops.EPI_SILU_MUL, avg_rows=avg, a_rows=arow)
     if isinstance(combine, tuple):
         residual, norm_w, eps = combine

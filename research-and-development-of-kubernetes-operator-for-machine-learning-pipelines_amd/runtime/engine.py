@@ -266,6 +266,12 @@ class EngineConfig:
     # weights" there): 3.8x fewer.  Dense TP = 1 models without LoRA; embedding, LM head and norms
     # stay bf16.  "bf16" changes no launch or allocation.
     weight_dtype: str = "bf16"
+    # element type of a MoE model's expert matrices (w13 / w2): "bf16", or "mxfp4" = the format
+    # above, every expert quantised on the device once loaded and served by moe_mx4.hip
+    # (ops.grouped_gemm_mx4).  MoE models at TP = EP = 1 with weight_dtype "bf16"; attention
+    # projections, router, embedding, LM head and norms stay bf16.  "bf16" changes no launch or
+    # allocation.
+    expert_weight_dtype: str = "bf16"
     # speculative decoding by prompt lookup (runtime/spec.py): up to ``spec_tokens`` (k <= 7) draft
     # tokens per row, found by matching the sequence's last ``spec_ngram_max`` .. ``spec_ngram_min``
     # tokens in its own history, are verified in one pass with the row's decode token; outputs are
@@ -420,6 +426,16 @@ class Engine:
                 raise ValueError('kv_cache_dtype="fp8" is not supported for MoE models / expert parallelism')
             if mc.head_dim != 128:
                 raise ValueError('kv_cache_dtype="fp8" needs head_dim 128')
+        if cfg.expert_weight_dtype not in ("bf16", "mxfp4"):
+            raise ValueError(f"expert_weight_dtype must be one of ['bf16', 'mxfp4'], not {cfg.expert_weight_dtype!r}")
+        if cfg.expert_weight_dtype == "mxfp4":
+            if not getattr(mc, "is_moe", False):
+                raise ValueError(f'expert_weight_dtype="mxfp4" needs a MoE model ({mc.name} is dense)')
+            if model.ps.tp.size > 1 or model.ps.ep.size > 1:
+                raise ValueError('expert_weight_dtype="mxfp4" needs tensor parallel size 1 and expert parallel size 1')
+            if cfg.weight_dtype != "bf16":
+                raise ValueError(f'expert_weight_dtype="mxfp4" is not served together with weight_dtype='
+                                 f'"{cfg.weight_dtype}"')
         wd = weight_dtype_check(cfg.weight_dtype)  # ValueError for an unknown name
         if wd != "bf16":
             if model.ps.tp.size > 1:
@@ -430,6 +446,10 @@ class Engine:
                 raise ValueError(f'weight_dtype="{wd}" does not serve LoRA adapters (max_adapters must be 0)')
             # before anything below sizes itself from the free memory
             (model.quantize_int4 if wd == "int4" else model.quantize_mxfp4)()
+        if cfg.expert_weight_dtype == "mxfp4":
+            # ValueError for an expert shape the packing does not take; before anything below
+            # sizes itself from the free memory
+            model.quantize_experts_mxfp4()
         self.spec_k = int(cfg.spec_tokens or 0)
         # optional callable (seq, cap) -> list[int]: replaces the device n-gram proposals (the
         # extension point of a draft-model proposer; lets tests force any acceptance pattern)
@@ -553,6 +573,8 @@ class Engine:
             self.stats["kv_cache_dtype"] = cfg.kv_cache_dtype
         if cfg.weight_dtype != "bf16":  # likewise: stats.get("weight_dtype", "bf16")
             self.stats["weight_dtype"] = cfg.weight_dtype
+        if cfg.expert_weight_dtype != "bf16":  # likewise
+            self.stats["expert_weight_dtype"] = cfg.expert_weight_dtype
         # one-step-ahead (async) scheduling state: the in-flight step, its token read-back
         # buffers (two pinned, alternating) and the event after its metadata upload.  Under TP
         # only the leader schedules (workers follow the host-side headers, StepSync); under EP
