@@ -309,7 +309,8 @@ class LlamaModel:
     def _forward_q4(self, ids, meta, kv) -> torch.Tensor:
         """The 4-bit-weights forward (TP = 1): the layer from its unfused blocks, every projection
         through ops.gemm_q4 or, for MXFP4 weights, ops.gemm_mx4 (the weight-streaming kernel up to
-        64 rows; dequantise + the bf16 GEMMs above, where gate_up keeps its fused SiLU-mul).  The
+        64 rows; MXFP4 up to ops.MX4_TILE_MAX_M rows: the fused tiled kernel, SiLU-mul in its
+        epilogue; dequantise + the bf16 GEMMs above, where gate_up keeps its fused SiLU-mul).  The
         stand-alone RoPE + cache writers serve QK-norm and fp8 KV as they do for bf16 weights."""
         eps = self.cfg.rms_eps
         gemm = ops.gemm_mx4 if self.weight_dtype == "mxfp4" else ops.gemm_q4

@@ -825,11 +825,15 @@ def gemm_q4(x: torch.Tensor, W, epi: int = EPI_NONE) -> torch.Tensor:
 
 
 # -------------------------------------------------------- mxfp4 weights --
-# W4A16 in OCP MXFP4 (csrc/gemm_mx4.hip; the format is ref.mx4_quantize's).  The same two routes as
-# int4: the weight-streaming kernel up to MX4_WS_MAX_M rows, above it the dequantiser into the
-# scratch of ``q4_reserve_scratch`` and the unchanged ``gemm``.
+# W4A16 in OCP MXFP4 (csrc/gemm_mx4.hip; the format is ref.mx4_quantize's).  Three routes: the
+# weight-streaming kernel up to MX4_WS_MAX_M rows; above it, up to MX4_TILE_MAX_M rows and for
+# N % 128 == 0, the fused tiled kernel (csrc/gemm_mx4t.hip: packed weights read once, A shared through
+# LDS, no scratch); everything else the dequantiser into the scratch of ``q4_reserve_scratch`` and the
+# unchanged ``gemm``.
 MX4_WS_KERNEL_MAX_M = 64  # gemm_mx4_kernel's MT limit (4 row tiles of 16)
 MX4_WS_MAX_M = min(MX4_WS_KERNEL_MAX_M, max(0, int(os.environ.get("MLOP_MX4_WS_MAX_M", "64"))))
+# the largest M the tiled kernel takes (profiles/mxfp4_tile.md); 0 = the dequantise route as before it
+MX4_TILE_MAX_M = max(0, int(os.environ.get("MLOP_MX4_TILE_MAX_M", "512")))
 
 
 class Mx4Weight:
@@ -873,7 +877,8 @@ def mx4_dequant(W: Mx4Weight, out: torch.Tensor | None = None) -> torch.Tensor:
 def gemm_mx4(x: torch.Tensor, W: Mx4Weight, epi: int = EPI_NONE) -> torch.Tensor:
     """y = epi(x @ dequant(W)^T) for a packed MXFP4 W.  M <= MX4_WS_MAX_M: gemm_mx4.hip (the scaled
     weights are exact bf16 MFMA operands, fp32 accumulation; ``ref.gemm_mx4``), SiLU-mul as the
-    separate interleaved kernel.  Larger M: dequantise, then ``gemm(x, scratch, epi)``."""
+    separate interleaved kernel.  M <= MX4_TILE_MAX_M and N % 128 == 0: gemm_mx4t.hip, the same
+    arithmetic tiled, SiLU-mul fused.  Otherwise: dequantise, then ``gemm(x, scratch, epi)``."""
     N, K = W.N, W.K
     if x.shape[-1] != K:
         raise ValueError(f"gemm_mx4: x has {x.shape[-1]} columns, the weight K = {K}")
@@ -882,12 +887,17 @@ def gemm_mx4(x: torch.Tensor, W: Mx4Weight, epi: int = EPI_NONE) -> torch.Tensor
     if not x.is_cuda:
         return gemm(x2, mx4_dequant(W), epi=epi).view(*lead, -1)
     M = x2.shape[0]
-    if M > MX4_WS_MAX_M or M == 0:
+    tile = MX4_WS_MAX_M < M <= MX4_TILE_MAX_M and N % 128 == 0 and epi in (EPI_NONE, EPI_SILU_MUL)
+    if (M > MX4_WS_MAX_M and not tile) or M == 0:
         wd = mx4_dequant(W, q4_reserve_scratch(x.device, N * K)[: N * K].view(N, K))
         return gemm(x2, wd, epi=epi).view(*lead, -1)
     _need_gpu()
     if x2.stride(-1) != 1 or x2.stride(0) % 8:
         x2 = x2.contiguous()
+    if tile:  # the fp32 partials of a split-K launch are allocated per call inside the op
+        y = torch.empty(M, N // 2 if epi == EPI_SILU_MUL else N, dtype=x.dtype, device=x.device)
+        torch.ops.mlop.gemm_mx4_tile(y, x2, W.qw, W.qe, N, epi, 0)
+        return y.view(*lead, -1)
     y = torch.empty(M, N, dtype=x.dtype, device=x.device)
     torch.ops.mlop.gemm_mx4(y, x2, W.qw, W.qe, N)
     if epi == EPI_SILU_MUL:

@@ -705,6 +705,33 @@ void gemm_mx4(Tensor out, Tensor a, Tensor qw, Tensor qe, int64_t N, int64_t rb)
               "gemm_mx4: shape or rb refused");
 }
 
+// the fused tiled kernel (gemm_mx4t.hip): ks 0 = the launcher's rule, else that many K splits; the
+// fp32 partials of a split launch are a per-call allocation (graph capture keeps it in its pool)
+void gemm_mx4_tile(Tensor out, Tensor a, Tensor qw, Tensor qe, int64_t N, int64_t epi, int64_t ks) {
+  check_a(a);
+  const int64_t M = a.size(0), K = a.size(1);
+  check_mx4(qw, qe, N, K);
+  TORCH_CHECK(M >= 1 && N % 128 == 0, "gemm_mx4_tile: M >= 1 and N % 128 == 0, not M = ", M, ", N = ", N);
+  TORCH_CHECK(epi == 0 || epi == 1, "gemm_mx4_tile: epi 0 or 1 (SiLU-mul)");
+  TORCH_CHECK(out.is_cuda() && out.scalar_type() == at::kBFloat16 && out.dim() == 2 && out.size(0) == M &&
+                  out.size(1) == (epi == 0 ? N : N / 2) && out.is_contiguous() && out.device() == a.device() &&
+                  qw.device() == a.device() && qe.device() == a.device(),
+              "gemm_mx4_tile: out bf16 [M, N] (epi 1: [M, N / 2]) contiguous on a's device");
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(a.data_ptr()) & 15) == 0, "a must be 16-B aligned");
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(out.data_ptr()) & 7) == 0, "out must be 8-B aligned");
+  if (ks == 0) ks = mlop::mx4_tile_ks((int)M, (int)N, (int)K);
+  TORCH_CHECK(ks >= 1 && ks <= K / 128, "gemm_mx4_tile: ks must leave every split a 128-wide K tile, not ", ks);
+  c10::DeviceGuard g(a.device());
+  Tensor slab;
+  if (ks > 1) slab = at::empty({ks, M, N}, a.options().dtype(at::kFloat));
+  TORCH_CHECK(mlop::launch_gemm_mx4_tile(a.data_ptr(), (int)a.stride(0), qw.data_ptr(), qe.data_ptr(), out.data_ptr(),
+                                         ks > 1 ? slab.data_ptr<float>() : nullptr, (int)M, (int)N, (int)K, (int)epi,
+                                         (int)ks, cur_stream()),
+              "gemm_mx4_tile: shape, epi or ks refused");
+}
+
+int64_t mx4_tile_ks(int64_t M, int64_t N, int64_t K) { return mlop::mx4_tile_ks((int)M, (int)N, (int)K); }
+
 void mx4_dequant(Tensor out, Tensor qw, Tensor qe) {
   check_bf16(out, "out");
   TORCH_CHECK(out.dim() == 2, "mx4_dequant: out bf16 [N, K]");
@@ -1458,6 +1485,8 @@ TORCH_LIBRARY(mlop, m) {
   m.def("q4_dequant(Tensor(a!) out, Tensor qw, Tensor qs) -> ()");
   m.def("gemm_mx4(Tensor(a!) out, Tensor a, Tensor qw, Tensor qe, int N, int rb=0) -> ()");
   m.def("mx4_dequant(Tensor(a!) out, Tensor qw, Tensor qe) -> ()");
+  m.def("gemm_mx4_tile(Tensor(a!) out, Tensor a, Tensor qw, Tensor qe, int N, int epi, int ks=0) -> ()");
+  m.def("mx4_tile_ks(int M, int N, int K) -> int", &mx4_tile_ks);
   m.def("grouped_gemm_mx4(Tensor(a!) out, Tensor a, Tensor qw, Tensor qe, Tensor offsets, int N, int epi, int rb=0, "
         "Tensor? a_rows=None) -> ()");
   m.def("moe_mx4_rb(int R, int E, int N, int epi) -> int", &moe_mx4_rb);
@@ -1501,6 +1530,7 @@ TORCH_LIBRARY_IMPL(mlop, CUDA, m) {
   m.impl("q4_dequant", &q4_dequant);
   m.impl("gemm_mx4", &gemm_mx4);
   m.impl("mx4_dequant", &mx4_dequant);
+  m.impl("gemm_mx4_tile", &gemm_mx4_tile);
   m.impl("grouped_gemm_mx4", &grouped_gemm_mx4);
   m.impl("grouped_gemm", &grouped_gemm);
   m.impl("gemm_add_rmsnorm", &gemm_add_rmsnorm);

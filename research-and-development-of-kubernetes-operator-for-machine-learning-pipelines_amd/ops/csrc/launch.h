@@ -152,6 +152,14 @@ bool launch_q4_dequant(void* out, const void* qw, const void* qs, int N, int K, 
 bool launch_gemm_mx4(const void* A, int lda, const void* qw, const void* qe, void* C, int ldc, int M, int N, int K,
                      int rb, hipStream_t st);
 bool launch_mx4_dequant(void* out, const void* qw, const void* qe, int N, int K, hipStream_t st);
+// the fused tiled form (gemm_mx4t.hip) of the same weights for any M >= 1, N % 128 == 0: epi 0: C bf16
+// [M, N]; 1: SiLU-mul of the gate / up interleaved columns, C [M, N / 2]; both contiguous.  ks = K
+// splits, 1 <= ks <= K / 128 (mx4_tile_ks: the launcher's rule, a pure function of the shape; 0 =
+// shape not taken); ks > 1 needs slab, fp32 [ks, M, N], and adds the reduce launch.  false: shape,
+// epi or ks refused, nothing launched
+int mx4_tile_ks(int M, int N, int K);
+bool launch_gemm_mx4_tile(const void* A, int lda, const void* qw, const void* qe, void* C, float* slab, int M, int N,
+                          int K, int epi, int ks, hipStream_t st);
 // MXFP4 expert weights (moe_mx4.hip): the pair above with the expert outermost (qw [E, N / 16, ...]).
 // Rows offsets[e] .. offsets[e + 1] of the R permuted rows belong to expert e (device int32 [E + 1]);
 // a_rows (or null): permuted row r is row a_rows[r] of A.  epi 0: C [R, N]; 1: SiLU-mul of the

@@ -24,7 +24,7 @@
 //     (ops.interleave_gate_up), so row block 2 p holds 16 gates and row block 2 p + 1 their ups:
 //     with RB even the thread that finishes (row, lane) of block 2 p also sums the same entry of
 //     block 2 p + 1, rounds both to bf16 as the unfused path stores them, and writes
-//     silu(g) * u to column 16 p + (lane & 15) of the [R, N / 2] output.  silu is moe_mx4_silu:
+//     silu(g) * u to column 16 p + (lane & 15) of the [R, N / 2] output.  silu is mx4_cvt.h's mx4_silu:
 //     common.h's silu_bf except for gates in (-88.7, -87.3), where that one's reciprocal is a
 //     denormal that v_rcp_f32 flushes (silu = -0 where fp32 division gives about -1e-36).
 #include "common.h"
@@ -34,17 +34,6 @@
 namespace mlop {
 
 namespace {
-
-// SiLU of a bf16-rounded gate, rounded to bf16.  d = 1 + exp(-g) above 2^126 (g < -87.3) has a
-// denormal reciprocal, which v_rcp_f32 returns as 0; there the reciprocal is taken of d 2^-32 and the
-// scale goes back in after the product, which is a normal fp32 again (d = inf, g < -88.7: -0, as
-// fp32 division gives).  Elsewhere s = 1 and the arithmetic is silu_bf's bit for bit.
-__device__ __forceinline__ float moe_mx4_silu(float g) {
-  const float gb = bf2f(f2bf(g));
-  const float d = 1.f + __expf(-gb);
-  const float s = d > 0x1p100f ? 0x1p-32f : 1.f;
-  return bf2f(f2bf(gb * __builtin_amdgcn_rcpf(d * s) * s));
-}
 
 // one chunk of <= 16 MT rows (rows m0 .. m0 + rows of the permuted order) against the expert's
 // row blocks nb0 .. nb0 + RB; red is the workgroup's LDS, [wave][(t RB + rb) 4 + r][lane]
@@ -168,7 +157,7 @@ __device__ __forceinline__ void moe_mx4_chunk(const uint16_t* __restrict__ A, in
 #pragma unroll
       for (int p = 0; p < RB / 2; ++p) {
         const float g = total((t * RB + 2 * p) * 4 + r), u = total((t * RB + 2 * p + 1) * 4 + r);
-        crow[8 * (nb0 + 2 * p) + (lane & 15)] = f2bf(moe_mx4_silu(g) * bf2f(f2bf(u)));
+        crow[8 * (nb0 + 2 * p) + (lane & 15)] = f2bf(mx4_silu(g) * bf2f(f2bf(u)));
       }
     }
   }

@@ -23,4 +23,16 @@ __device__ __forceinline__ bf16x8 mx4_word(uint32_t w, float scale) {
   return __builtin_bit_cast(bf16x8, o);
 }
 
+// SiLU of a bf16-rounded gate, rounded to bf16 (the fused SiLU-mul epilogues of moe_mx4.hip and
+// gemm_mx4t.hip).  d = 1 + exp(-g) above 2^126 (g < -87.3) has a
+// denormal reciprocal, which v_rcp_f32 returns as 0; there the reciprocal is taken of d 2^-32 and the
+// scale goes back in after the product, which is a normal fp32 again (d = inf, g < -88.7: -0, as
+// fp32 division gives).  Elsewhere s = 1 and the arithmetic is silu_bf's bit for bit.
+__device__ __forceinline__ float mx4_silu(float g) {
+  const float gb = bf2f(f2bf(g));
+  const float d = 1.f + __expf(-gb);
+  const float s = d > 0x1p100f ? 0x1p-32f : 1.f;
+  return bf2f(f2bf(gb * __builtin_amdgcn_rcpf(d * s) * s));
+}
+
 }  // namespace mlop

@@ -4,6 +4,8 @@ round by round in one process.
     python scripts/bench_mx4.py kernel          # the projections: us, achieved TB/s of packed bytes
     python scripts/bench_mx4.py rb              # gemm_mx4_kernel with 1 / 2 / 4 row blocks per workgroup
     python scripts/bench_mx4.py engine          # a Llama-3-8B engine with bf16, int4 and mxfp4 weights
+    python scripts/bench_mx4.py tile            # gemm_mx4t.hip against bf16, the dequantise route and the streaming kernel
+    python scripts/bench_mx4.py tile-engine     # the mxfp4 engine with MLOP_MX4_TILE_MAX_M = 0 and --tile-max-m, alternating
 
 kernel: the four Llama-3-8B projections and 70B's gate_up.  M <= 64: ``ops.gemm_mx4`` and ``ops.gemm_q4``
 (the weight-streaming kernels) against ``ops.gemm`` over the bf16 weight; M = 128, 512, 2048:
@@ -11,10 +13,17 @@ dequantise + GEMM against the GEMM alone.  Each timed window flushes nothing: li
 every call streams weights that the other projections' traffic has pushed out of the caches (the
 weights rotate over enough copies to exceed them).  Device events; one JSON line per (shape, M) with
 the median of the rounds and their min / max.
+
+tile: per shape and M the bf16 ``ops.gemm``, dequantise + GEMM, the tiled op with the launcher's split
+and (o, down) every forced split of --ks, and the streaming kernel up to 64 rows; TB/s of packed bytes
+and TF/s (2 M N K) from the shapes.  tile-engine: decode at batch 64 and 256 and prefill 4 x 2048, each
+knob value in a fresh child process (the knob is read at import), alternating round by round.
 """
 import argparse
 import json
+import os
 import statistics
+import subprocess
 import sys
 from pathlib import Path
 
@@ -61,11 +70,11 @@ def _stats(row, name, ts, nbytes):
                 f"{name}_TBps": round(nbytes / m / 1e6, 3)})
 
 
-def _weights(N, K, dev, bf16=True):
+def _weights(N, K, dev, bf16=True, q4=True):
     copies = max(2, -(-CACHE_BYTES // ops.q4_bytes(N, K)))
     copies = min(copies, max(2, int(6 * 2 ** 30 // (2 * N * K))))  # bf16 copies: at most 6 GiB
     wb = [(0.02 * torch.randn(N, K, device=dev)).to(torch.bfloat16) for _ in range(copies)]
-    wq = [ops.q4_quantize_pack(w) for w in wb]
+    wq = [ops.q4_quantize_pack(w) for w in wb] if q4 else None
     wm = [ops.mx4_quantize_pack(w) for w in wb]
     return copies, (wb if bf16 else None), wq, wm
 
@@ -157,17 +166,94 @@ def bench_engine(args):
             torch.cuda.empty_cache()
 
 
+def bench_tile(args):
+    dev = torch.device("cuda", 0)
+    ops.load()
+    for name, (N, K) in SHAPES.items():
+        if args.shapes and name not in args.shapes:
+            continue
+        copies, wb, _, wm = _weights(N, K, dev, q4=False)
+        scr = ops.q4_reserve_scratch(dev, N * K)[: N * K].view(N, K)
+        for M in args.rows:
+            x = torch.randn(M, K, device=dev, dtype=torch.bfloat16)
+            y = torch.empty(M, N, device=dev, dtype=torch.bfloat16)
+            iters = max(8, min(200, int(2e9 // (N * K * max(M, 16) // 16))))
+
+            def tile(ks):
+                return lambda i: torch.ops.mlop.gemm_mx4_tile(y, x, wm[i % copies].qw, wm[i % copies].qe, N, 0, ks)
+
+            ks0 = int(torch.ops.mlop.mx4_tile_ks(M, N, K))
+            fns = {"bf16": lambda i: ops.gemm(x, wb[i % copies]),
+                   "dequant": lambda i: ops.gemm(x, ops.mx4_dequant(wm[i % copies], scr)), "tile": tile(0)}
+            if M <= ops.MX4_WS_KERNEL_MAX_M:
+                fns["ws"] = lambda i: torch.ops.mlop.gemm_mx4(y, x, wm[i % copies].qw, wm[i % copies].qe, N, 0)
+            if name in ("8b-o", "8b-down"):
+                fns.update({f"tile_ks{ks}": tile(ks) for ks in args.ks if ks != ks0 and ks <= K // 128})
+            t = _rounds(fns, copies, iters, args.rounds)
+            row = dict(bench="tile", shape=name, N=N, K=K, M=M, ks=ks0)
+            for k, ts in t.items():
+                _stats(row, k, ts, 2 * N * K if k == "bf16" else ops.mx4_bytes(N, K))
+                row[f"{k}_TFps"] = round(2 * M * N * K / statistics.median(ts) / 1e6, 1)
+            print(json.dumps(row), flush=True)
+        del wb, wm
+        torch.cuda.empty_cache()
+
+
+def _tile_engine_child(args):
+    """One engine in this process (MLOP_MX4_TILE_MAX_M came with the environment): one JSON row."""
+    dev = torch.device("cuda", 0)
+    ops.load()
+    cfg = get_config("llama3-8b", num_layers=args.layers)
+    g = torch.Generator().manual_seed(0)
+    eng = Engine(build_model(cfg, device=dev, seed=0),
+                 EngineConfig(max_num_seqs=256, max_num_batched_tokens=2048, max_model_len=4096, num_kv_blocks=4096,
+                              graph_buckets=(64, 256), weight_dtype=args.weights))
+    row = dict(bench="tile-engine", weight_dtype=args.weights, tile_max_m=ops.MX4_TILE_MAX_M, layers=cfg.num_layers)
+
+    def timed(prompts, sp):
+        torch.cuda.synchronize()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        eng.generate(prompts, sp)
+        b.record()
+        b.synchronize()
+        return a.elapsed_time(b) / 1e3
+
+    for batch in (64, 256):
+        prompts = [torch.randint(2, 1000, (16,), generator=g).tolist() for _ in range(batch)]
+        eng.generate(prompts, SamplingParams(max_tokens=8, ignore_eos=True))  # warm-up, graph capture
+        row[f"decode_tok_s_b{batch}"] = round(batch * args.gen / timed(prompts, SamplingParams(max_tokens=args.gen, ignore_eos=True)), 1)
+    prompts = [torch.randint(2, 1000, (2048,), generator=g).tolist() for _ in range(4)]
+    eng.generate(prompts[:1], SamplingParams(max_tokens=1, ignore_eos=True))
+    row["prefill_tok_s"] = round(4 * 2048 / timed(prompts, SamplingParams(max_tokens=1, ignore_eos=True)), 1)
+    print(json.dumps(row), flush=True)
+
+
+def bench_tile_engine(args):
+    if args.child:
+        return _tile_engine_child(args)
+    base = [sys.executable, __file__, "tile-engine", "--child", "--layers", str(args.layers), "--gen", str(args.gen)]
+    for _ in range(args.rounds):
+        for wd, knob in (("bf16", "0"), ("mxfp4", "0"), ("mxfp4", str(args.tile_max_m))):
+            subprocess.run(base + ["--weights", wd], env=dict(os.environ, MLOP_MX4_TILE_MAX_M=knob), check=True, timeout=900)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("what", choices=["kernel", "rb", "engine"])
+    ap.add_argument("what", choices=["kernel", "rb", "engine", "tile", "tile-engine"])
     ap.add_argument("--rows", type=int, nargs="*", default=[1, 4, 8, 16, 32, 64, 128, 512, 2048])
     ap.add_argument("--shapes", nargs="*", default=[])
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--layers", type=int, default=32)
     ap.add_argument("--gen", type=int, default=128)
+    ap.add_argument("--ks", type=int, nargs="*", default=[1, 2, 4, 8], help="tile: forced K splits on o and down")
+    ap.add_argument("--tile-max-m", type=int, default=1024, help="tile-engine: the knob value set against 0")
+    ap.add_argument("--weights", default="mxfp4", help="tile-engine child: weight_dtype")
+    ap.add_argument("--child", action="store_true", help="tile-engine: run one engine in this process")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_mx4 measures on a GPU"
-    {"kernel": bench_kernel, "rb": bench_rb, "engine": bench_engine}[args.what](args)
+    {"kernel": bench_kernel, "rb": bench_rb, "engine": bench_engine, "tile": bench_tile,
+     "tile-engine": bench_tile_engine}[args.what](args)
 
 
 if __name__ == "__main__":
