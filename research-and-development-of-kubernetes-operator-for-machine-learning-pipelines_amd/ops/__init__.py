@@ -910,8 +910,13 @@ def gemm_mx4(x: torch.Tensor, W: Mx4Weight, epi: int = EPI_NONE) -> torch.Tensor
 # outermost.  The streaming kernel serves a launch whose experts average up to
 # MX4_MOE_MAX_AVG_ROWS rows (any single expert may hold more: it is walked in 64-row chunks);
 # above, the layer's experts are dequantised into the scratch of ``q4_reserve_scratch`` and the
-# unchanged ``grouped_gemm`` runs.
+# unchanged ``grouped_gemm`` runs.  Between them, for N % 128 == 0, the fused tiled kernel
+# (csrc/moe_mx4t.hip: a weight tile converted once per 128 rows, A shared through LDS, no scratch)
+# takes MX4_MOE_TILE_MIN_AVG_ROWS < avg_rows <= MX4_MOE_TILE_MAX_AVG_ROWS (profiles/moe_mxfp4_tile.md);
+# MAX = 0 leaves the two routes above as they were before it.
 MX4_MOE_MAX_AVG_ROWS = max(0, int(os.environ.get("MLOP_MX4_MOE_MAX_AVG_ROWS", "256")))
+MX4_MOE_TILE_MIN_AVG_ROWS = max(0, int(os.environ.get("MLOP_MX4_MOE_TILE_MIN_AVG_ROWS", "32")))
+MX4_MOE_TILE_MAX_AVG_ROWS = max(0, int(os.environ.get("MLOP_MX4_MOE_TILE_MAX_AVG_ROWS", "512")))
 
 
 class Mx4Experts:
@@ -959,8 +964,10 @@ def mx4_experts_dequant(W: Mx4Experts, out: torch.Tensor | None = None) -> torch
 
 def grouped_gemm_mx4(xp, W: Mx4Experts, offsets, epi: int = EPI_NONE, avg_rows: int | None = None, a_rows=None):
     """``grouped_gemm`` over packed MXFP4 experts: the same rows, ``offsets`` / ``a_rows`` meaning,
-    output order and epilogues.  ``avg_rows`` <= MX4_MOE_MAX_AVG_ROWS: moe_mx4.hip in one launch.
-    Above: dequantise the layer's experts, then ``grouped_gemm``.  CPU tensors take the reference."""
+    output order and epilogues.  MX4_MOE_TILE_MIN_AVG_ROWS < ``avg_rows`` <= MX4_MOE_TILE_MAX_AVG_ROWS
+    and N % 128 == 0: moe_mx4t.hip in one launch.  Otherwise ``avg_rows`` <= MX4_MOE_MAX_AVG_ROWS:
+    moe_mx4.hip in one launch; above: dequantise the layer's experts, then ``grouped_gemm``.  CPU
+    tensors take the reference."""
     E, N, K = W.E, W.N, W.K
     if xp.shape[-1] != K or offsets.numel() != E + 1:
         raise ValueError(f"grouped_gemm_mx4: x has {xp.shape[-1]} columns and offsets {offsets.numel()} entries; "
@@ -969,7 +976,9 @@ def grouped_gemm_mx4(xp, W: Mx4Experts, offsets, epi: int = EPI_NONE, avg_rows: 
         return grouped_gemm(xp, mx4_experts_dequant(W), offsets, epi=epi, avg_rows=avg_rows, a_rows=a_rows)
     R = xp.shape[0] if a_rows is None else a_rows.numel()
     rows = avg_rows if avg_rows is not None else max(1, R // E)
-    if rows > MX4_MOE_MAX_AVG_ROWS:
+    tile = (MX4_MOE_TILE_MIN_AVG_ROWS < rows <= MX4_MOE_TILE_MAX_AVG_ROWS and N % 128 == 0
+            and epi in (EPI_NONE, EPI_SILU_MUL))
+    if rows > MX4_MOE_MAX_AVG_ROWS and not tile:
         wd = mx4_experts_dequant(W, q4_reserve_scratch(xp.device, E * N * K)[: E * N * K])
         return grouped_gemm(xp, wd, offsets, epi=epi, avg_rows=avg_rows, a_rows=a_rows)
     _need_gpu()
@@ -978,7 +987,9 @@ def grouped_gemm_mx4(xp, W: Mx4Experts, offsets, epi: int = EPI_NONE, avg_rows: 
     if xp.stride(-1) != 1 or xp.stride(0) % 8:
         xp = xp.contiguous()
     out = torch.empty(R, N if epi == EPI_NONE else N // 2, dtype=xp.dtype, device=xp.device)
-    if R > 0:
+    if R > 0 and tile:
+        torch.ops.mlop.grouped_gemm_mx4_tile(out, xp, W.qw, W.qe, offsets, N, epi, a_rows)
+    elif R > 0:
         torch.ops.mlop.grouped_gemm_mx4(out, xp, W.qw, W.qe, offsets, N, epi, 0, a_rows)
     return out
 

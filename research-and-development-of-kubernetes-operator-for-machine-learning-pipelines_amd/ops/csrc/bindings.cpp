@@ -795,6 +795,35 @@ void grouped_gemm_mx4(Tensor out, Tensor a, Tensor qw, Tensor qe, Tensor offsets
               "grouped_gemm_mx4: shape or rb refused");
 }
 
+// the fused tiled kernel over the same experts (moe_mx4t.hip): grouped_gemm_mx4's contract at N % 128 == 0
+void grouped_gemm_mx4_tile(Tensor out, Tensor a, Tensor qw, Tensor qe, Tensor offsets, int64_t N, int64_t epi,
+                           std::optional<Tensor> a_rows) {
+  check_a(a);
+  check_bf16(out, "out"); check_i32(offsets, "offsets");
+  const int64_t R = out.size(0), K = a.size(1), E = offsets.numel() - 1;
+  TORCH_CHECK(E >= 1 && offsets.is_contiguous(), "offsets must be int32 [E + 1]");
+  check_mx4(qw, qe, E * N, K);
+  TORCH_CHECK(N % 128 == 0, "grouped_gemm_mx4_tile: N % 128 == 0, not N = ", N);
+  TORCH_CHECK(epi == 0 || epi == 1, "grouped_gemm_mx4_tile: epi 0 or 1 (SiLU-mul)");
+  TORCH_CHECK(out.dim() == 2 && out.is_contiguous() && out.size(1) == (epi == 0 ? N : N / 2),
+              "grouped_gemm_mx4_tile: out bf16 [R, N] (epi 1: [R, N / 2]) contiguous");
+  TORCH_CHECK(out.device() == a.device() && qw.device() == a.device() && qe.device() == a.device() &&
+                  offsets.device() == a.device(), "grouped_gemm_mx4_tile: one device");
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(a.data_ptr()) & 15) == 0, "a must be 16-B aligned");
+  if (a_rows) {  // the permuted rows are out's and a holds the token rows they name
+    check_i32(*a_rows, "a_rows");
+    TORCH_CHECK(a_rows->is_contiguous() && a_rows->numel() >= R && a_rows->device() == a.device(),
+                "a_rows [R]: every permuted row's token row");
+  } else {
+    TORCH_CHECK(a.size(0) >= R, "grouped_gemm_mx4_tile: a [R, K]");
+  }
+  c10::DeviceGuard g(a.device());
+  TORCH_CHECK(mlop::launch_moe_mx4_tile(a.data_ptr(), (int)a.stride(0), a_rows ? a_rows->data_ptr<int>() : nullptr,
+                                        qw.data_ptr(), qe.data_ptr(), offsets.data_ptr<int>(), out.data_ptr(), (int)R,
+                                        (int)E, (int)N, (int)K, (int)epi, cur_stream()),
+              "grouped_gemm_mx4_tile: shape or epi refused");
+}
+
 int64_t moe_mx4_rb(int64_t R, int64_t E, int64_t N, int64_t epi) {
   return mlop::moe_mx4_rb((int)R, (int)E, (int)N, (int)epi);
 }
@@ -1489,6 +1518,8 @@ TORCH_LIBRARY(mlop, m) {
   m.def("mx4_tile_ks(int M, int N, int K) -> int", &mx4_tile_ks);
   m.def("grouped_gemm_mx4(Tensor(a!) out, Tensor a, Tensor qw, Tensor qe, Tensor offsets, int N, int epi, int rb=0, "
         "Tensor? a_rows=None) -> ()");
+  m.def("grouped_gemm_mx4_tile(Tensor(a!) out, Tensor a, Tensor qw, Tensor qe, Tensor offsets, int N, int epi, "
+        "Tensor? a_rows=None) -> ()");
   m.def("moe_mx4_rb(int R, int E, int N, int epi) -> int", &moe_mx4_rb);
   m.def("flash_prefill(Tensor(a!) out, Tensor q, Tensor k_cache, Tensor v_cache, Tensor block_tables, "
         "Tensor ptile_seq, Tensor ptile_q0, Tensor q_start, Tensor q_len, Tensor ctx_len, float scale, "
@@ -1532,6 +1563,7 @@ TORCH_LIBRARY_IMPL(mlop, CUDA, m) {
   m.impl("mx4_dequant", &mx4_dequant);
   m.impl("gemm_mx4_tile", &gemm_mx4_tile);
   m.impl("grouped_gemm_mx4", &grouped_gemm_mx4);
+  m.impl("grouped_gemm_mx4_tile", &grouped_gemm_mx4_tile);
   m.impl("grouped_gemm", &grouped_gemm);
   m.impl("gemm_add_rmsnorm", &gemm_add_rmsnorm);
   m.impl("gemm_res_ss", &gemm_res_ss);

@@ -168,6 +168,12 @@ bool launch_gemm_mx4_tile(const void* A, int lda, const void* qw, const void* qe
 int moe_mx4_rb(int R, int E, int N, int epi);
 bool launch_moe_mx4(const void* A, int lda, const int* a_rows, const void* qw, const void* qe, const int* offsets,
                     void* C, int ldc, int R, int E, int N, int K, int epi, int rb, hipStream_t st);
+// the fused tiled form (moe_mx4t.hip) of the same experts, offsets, a_rows and epilogues for
+// N % 128 == 0, made for experts of more than 64 rows: C contiguous; the grid is a function of
+// (R, E, N) alone.  R < 1 launches nothing and is true.  false: N % 128, K % 128, E < 1 or an epi
+// other than 0 / 1 (nothing launched)
+bool launch_moe_mx4_tile(const void* A, int lda, const int* a_rows, const void* qw, const void* qe,
+                         const int* offsets, void* C, int R, int E, int N, int K, int epi, hipStream_t st);
 void launch_gemv_rs(const void* A, int lda, const void* B, void* C, int ldc, int M, int N, int K, int epi,
                     const RopeEpi& re, float eps, hipStream_t st);
 void launch_gemv_res(const void* A, int lda, const void* B, void* residual, int M, int N, int K, hipStream_t st);

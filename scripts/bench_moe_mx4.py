@@ -7,8 +7,8 @@ alternating round by round in one process.
 kernel: one layer's experts at Mixtral-8x7B (8 experts, top-2) and Qwen3-30B-A3B (128 experts, top-8)
 shapes; T tokens routed uniformly at random (distinct experts per token), sorted by ``ops.moe_permute``.
 Per (model, T): ``ops.grouped_gemm`` over bf16 experts, ``ops.grouped_gemm_mx4`` forced onto the
-streaming kernel, and forced onto dequantise + grouped GEMM (the two sides of
-MLOP_MX4_MOE_MAX_AVG_ROWS).  Weight copies and routings rotate with coprime periods so that a call
+streaming kernel, forced onto dequantise + grouped GEMM (the two sides of
+MLOP_MX4_MOE_MAX_AVG_ROWS, the tile route off) and forced onto the fused tiled kernel (moe_mx4t.hip).  Weight copies and routings rotate with coprime periods so that a call
 streams weights the calls before it have pushed out of the caches.  Device events; one JSON line per
 (model, projection, T) with the median of the rounds and their min / max.
 """
@@ -72,14 +72,16 @@ def bench_kernel(args):
             for proj, epi in (("gate_up", ops.EPI_SILU_MUL), ("down", ops.EPI_NONE)):
                 a_of = (lambda r: r[0]) if proj == "gate_up" else (lambda r: r[1])
 
-                def mx4(i, limit):
+                def mx4(i, limit, tile=False):
                     r = routes[i % ROUTINGS]
                     ops.MX4_MOE_MAX_AVG_ROWS = limit
+                    ops.MX4_MOE_TILE_MIN_AVG_ROWS, ops.MX4_MOE_TILE_MAX_AVG_ROWS = 0, (1 << 30 if tile else 0)
                     return ops.grouped_gemm_mx4(a_of(r), wm[proj][i % copies], r[2], epi=epi, avg_rows=avg)
 
                 fns = {"bf16": lambda i: ops.grouped_gemm(a_of(routes[i % ROUTINGS]), wb[proj][i % copies],
                                                           routes[i % ROUTINGS][2], epi=epi, avg_rows=avg),
-                       "mxfp4_kernel": lambda i: mx4(i, 1 << 30), "mxfp4_dequant": lambda i: mx4(i, 0)}
+                       "mxfp4_kernel": lambda i: mx4(i, 1 << 30), "mxfp4_dequant": lambda i: mx4(i, 0),
+                       "mxfp4_tile": lambda i: mx4(i, 0, True)}
                 iters = max(8, min(200, 4096 // max(16, T)))
                 ts = {n: [] for n in fns}
                 for _ in range(args.rounds):
@@ -127,7 +129,7 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("what", choices=["kernel", "engine"])
     ap.add_argument("--models", nargs="*", default=list(MODELS))
-    ap.add_argument("--tokens", type=int, nargs="*", default=[1, 4, 16, 64, 256, 1024])
+    ap.add_argument("--tokens", type=int, nargs="*", default=[1, 4, 16, 64, 256, 1024, 2048, 4096])
     ap.add_argument("--batches", type=int, nargs="*", default=[1, 8, 64, 512])
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--layers", type=int, default=8)
